@@ -7,7 +7,14 @@ A "step" = one full ``solvers::lanczos_two_pass`` call (pass one, f(T_k) solve, 
 two), the window the reference times (src/bin/tradeoff.rs:265-288). Inputs (A, b) are
 resident in HBM before the timed region; x stays in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up the operator, warms up, times the K solves, writes x of the last one
+to DIR/x.npy when --dump-outputs is given, and prints the line: `value`, `ms_per_step`
+and the `roofline` read off the events recorded inside those same solves. Every other
+leg described below (the parity block, CPU baselines, PCIe, one-pass, the other configs
+and sizes, isolated kernel timings; at N > 1 the one-GPU reference, the exchange timing,
+configs[4] and the replicas) runs only with --full.
 
 N > 1: when started without torch.distributed.run's environment (no WORLD_SIZE), this
 process launches ``python -m torch.distributed.run --nproc-per-node N ... bench.py`` as
@@ -70,6 +77,18 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="beside the timed solves, everything else this benchmark measures or "
+                        "checks: isolated kernel timings, the untimed one-graph solve, PCIe, "
+                        "one-pass, the other configs, 5M arcs, the CPU baselines, the parity "
+                        "block; N > 1: the one-GPU reference, the exchange timing, configs[4] "
+                        "partitioned and the replicas. Without it a run only sets up, warms "
+                        "up, times the K solves and prints the line, and the switches of "
+                        "those legs below are not consulted")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed solves, write what the last of them returned to "
+                        "DIR/<name>.npy: x.npy, the solution vector (float64; N > 1: "
+                        "assembled from every rank's rows, written by rank 0)")
     p.add_argument("--k", type=int, default=500)
     p.add_argument("--f", choices=("inv", "exp"), default="inv",
                    help="built-in f(T_k) of the timed solve (inv: the headline, configs[2]; "
@@ -126,6 +145,25 @@ def parse(argv=None):
     p.add_argument("--child-timeout", type=float, default=CHILD_TIMEOUT_S,
                    help="N>1: seconds the parent waits for the torchrun child")
     return p.parse_args(argv)
+
+
+def plain_run(args) -> None:
+    """Without --full: only the timed solves of the line's `value`. Every other leg is
+    switched off, whatever its own switch says (`headline_only` also drops the isolated
+    kernel timings and the untimed one-graph solve)."""
+    args.headline_only = 1
+    args.other_configs = args.one_pass = args.pcie = args.scale_ref = 0
+    args.cpu_baseline = args.single_ref = args.parity = 0
+    args.configs4 = args.replicas = 0
+
+
+def dump_outputs(directory: str, **arrays) -> None:
+    """--dump-outputs: each array the timed solve returned, as DIR/<name>.npy (float64)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"),
+                np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def launch_command(argv, nproc: int, port: int) -> list:
@@ -545,7 +583,25 @@ def run_replicas(args, rank: int, world: int, dist, device: int) -> dict:
                        "x_expected": expected, "x_every_rank": [e["x"] for e in every]}}
 
 
-def partitioned_solve(args, arcs: int, rank: int, world: int, dist, dctx, device: int) -> dict:
+def exchange_block(op, iters: int, steps_taken: int, solve_s: float) -> dict:
+    """The partitioned line's `exchange` (--full): both exchange timing ids (collective,
+    every rank together) and the fraction of a solve they make."""
+    from tpl_amd import _lib
+    try:  # a diagnostic: its failure must not cost the measured line
+        ex1 = op.profile_kernel(_lib.TPL_KERNEL_EXCHANGE_P1, iters)
+        ex2 = op.profile_kernel(_lib.TPL_KERNEL_EXCHANGE_P2, iters)
+        comm_ms = (steps_taken * ex1[0] + (steps_taken - 1) * ex2[0]) / 1000.0
+        return {"pass1_us_per_step": round(ex1[0], 3),
+                "pass2_us_per_step": round(ex2[0], 3),
+                "bytes_received_per_step": [int(ex1[1]), int(ex2[1])],
+                "ms_per_solve": round(comm_ms, 3),
+                "comm_frac": round(comm_ms / (1000.0 * solve_s), 4)}
+    except Exception as e:  # noqa: BLE001
+        return {"error": str(e)}
+
+
+def partitioned_solve(args, arcs: int, rank: int, world: int, dist, dctx, device: int,
+                      dump_dir: str = None) -> dict:
     """ONE row-partitioned lanczos_two_pass (k = args.k, f = args.f) of the `arcs` workload
     over the `world` ranks (DistHipCsrOp, --dist-mode; RCCL all-gathers inside the pass
     graphs): K timed solves between barriers, max over ranks (strong
@@ -643,6 +699,8 @@ def partitioned_solve(args, arcs: int, rank: int, world: int, dist, dctx, device
         x_full = np.zeros(n)
         for rows, xs in parts:
             x_full[rows] = xs
+        if dump_dir:
+            dump_outputs(dump_dir, x=x_full)
         res["config"]["x_sha256_16"] = x_digest(x_full)
         prefix = {500000: "configs2", ARCS_SCALE: "configs4"}.get(arcs)
         if args.parity and prefix and (args.k, args.f) == (500, "inv"):
@@ -680,17 +738,8 @@ def partitioned_solve(args, arcs: int, rank: int, world: int, dist, dctx, device
         barrier()
     # SURVEY.md §8(e) "comm fraction": the exchanges of one pass-one / pass-two step (rank
     # totals + all-gathers, as the pass graphs issue them) timed alone, every rank together
-    try:  # a diagnostic: its failure must not cost the measured line
-        ex1 = op.profile_kernel(_lib.TPL_KERNEL_EXCHANGE_P1, args.profile_iters)
-        ex2 = op.profile_kernel(_lib.TPL_KERNEL_EXCHANGE_P2, args.profile_iters)
-        comm_ms = (steps_taken * ex1[0] + (steps_taken - 1) * ex2[0]) / 1000.0
-        res["exchange"] = {"pass1_us_per_step": round(ex1[0], 3),
-                           "pass2_us_per_step": round(ex2[0], 3),
-                           "bytes_received_per_step": [int(ex1[1]), int(ex2[1])],
-                           "ms_per_solve": round(comm_ms, 3),
-                           "comm_frac": round(comm_ms / (1000.0 * solve_s), 4)}
-    except Exception as e:  # noqa: BLE001
-        res["exchange"] = {"error": str(e)}
+    if args.full:
+        res["exchange"] = exchange_block(op, args.profile_iters, steps_taken, solve_s)
     if world > 1 and mode == "replicated" and rank == 0:
         pred = predicted_block(world, args.k, steps_taken, solve_s, rank_share_file(arcs))
         if pred is not None:
@@ -721,7 +770,8 @@ def multi_line(head: dict, world: int, args) -> dict:
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
             "status": "ok"}
     line.update({k: head[k] for k in keep if k in head})
-    line["parity"] = parity_block(dict(head.get("parity", {})))
+    if getattr(args, "full", True):  # a plain run checks nothing: no block, not an empty one
+        line["parity"] = parity_block(dict(head.get("parity", {})))
     return line
 
 
@@ -732,7 +782,8 @@ def sub_phase_failed(line: dict, name: str, status: str, detail: str) -> dict:
     line[name] = {"status": status, "detail": detail, "last_stage_rank0": _PROGRESS["stage"],
                   "after_s": round(time.time() - _PROGRESS["t0"], 1)}
     line["status"] = f"{name}: {status}"
-    line["parity"]["all_ok"] = False
+    if "parity" in line:
+        line["parity"]["all_ok"] = False
     return line
 
 
@@ -779,7 +830,7 @@ def run_multi(args, rank: int, world: int, dist, device: int) -> None:
                        transport=os.environ.get("TPL_DIST_TRANSPORT", "rccl"))
     stage_marker("comm_init")
     arcs = args.arcs or 500000
-    head = partitioned_solve(args, arcs, rank, world, dist, dctx, device)
+    head = partitioned_solve(args, arcs, rank, world, dist, dctx, device, args.dump_outputs)
     line = multi_line(head, world, args)
     _PROGRESS["line"] = line
     if args.configs4 and world > 1 and arcs != ARCS_SCALE:
@@ -913,6 +964,8 @@ def run_parent(argv, nproc: int, timeout: float, cmd=None) -> int:
 
 def main():
     args = parse()
+    if not args.full:
+        plain_run(args)
     if args.headline_only:
         args.other_configs = args.one_pass = args.pcie = args.scale_ref = 0
         args.cpu_baseline = args.single_ref = 0
@@ -1050,6 +1103,8 @@ def main():
     iters = args.steps * steps_taken
     value = iters / dt
     x_host = x_dev.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x=x_host)
     # parity: every timed workload's result against the digest the CPU oracle computed
     # in the device's reduction order (tests/golden/parity.json), outside the timed region
     expected = expected_parity() if args.parity else {}

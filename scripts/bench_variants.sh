@@ -4,7 +4,7 @@
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 for name in "$@"; do
-  TPL_LIB_PATH=$ROOT/two-pass-lanczos_amd/variants/libtpl_$name.so timeout -k 10 200 python bench.py --one-pass 0 --other-configs 0 --cpu-baseline 0 --pcie 0 --steps 5 > /tmp/bv.log 2>&1 || { echo "$name failed"; tail -5 /tmp/bv.log; exit 1; }
+  TPL_LIB_PATH=$ROOT/two-pass-lanczos_amd/variants/libtpl_$name.so timeout -k 10 200 python bench.py --full --one-pass 0 --other-configs 0 --cpu-baseline 0 --pcie 0 --steps 5 > /tmp/bv.log 2>&1 || { echo "$name failed"; tail -5 /tmp/bv.log; exit 1; }
   python - "$name" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/bv.log").read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ tail -5 "$OUT/pytest_gpu.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc=$rc: stopping"; exit $rc; fi
 [ "${SKIP_BENCH:-0}" = "1" ] && exit $rc
 echo "== bench"
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 3; }
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 3; }
 tail -2 "$OUT/bench.log"
 [ "${SKIP_PROF:-0}" = "1" ] && exit $rc
 echo "== rocprofv3 kernel trace"

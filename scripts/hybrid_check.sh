@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 cd "$ROOT"
-timeout -k 10 400 python bench.py --partition 1 --arcs 5000000 --steps 5 --warmup 1 > "$OUT/hybrid1_5m.log" 2>&1 || { tail -20 "$OUT/hybrid1_5m.log"; exit 3; }
+timeout -k 10 400 python bench.py --full --partition 1 --arcs 5000000 --steps 5 --warmup 1 > "$OUT/hybrid1_5m.log" 2>&1 || { tail -20 "$OUT/hybrid1_5m.log"; exit 3; }
 tail -1 "$OUT/hybrid1_5m.log"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/hybrid_prof" -o run --output-format csv -- python3 "$ROOT/bench.py" --partition 1 --arcs 5000000 --steps 3 --warmup 1 --single-ref 0 > "$OUT/hybrid_prof.log" 2>&1 || { tail -20 "$OUT/hybrid_prof.log"; exit 4; }

@@ -12,7 +12,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -2 "$OUT/pytest_gpu.log"
 fi
 echo "== bench"
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 3; }
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 3; }
 tail -1 "$OUT/bench.log" | cut -c1-600
 [ "${SKIP_PROF:-0}" = "1" ] && exit 0
 echo "== rocprofv3 kernel trace"

@@ -27,6 +27,6 @@ if [ $# -gt 0 ]; then
 fi
 if [ "${REH:-0}" = "1" ]; then
   echo "== rehearsal: bench.py --gpus 2, both ranks on GPU 0, host transport"
-  TPL_DEVICE=0 TPL_DIST_TRANSPORT=host timeout -k 10 700 python bench.py --gpus 2 --steps 3 --warmup 1 --child-timeout 650 > "$OUT/reh2.log" 2>&1 || { echo "rehearsal failed"; tail -20 "$OUT/reh2.log"; exit 4; }
+  TPL_DEVICE=0 TPL_DIST_TRANSPORT=host timeout -k 10 700 python bench.py --full --gpus 2 --steps 3 --warmup 1 --child-timeout 650 > "$OUT/reh2.log" 2>&1 || { echo "rehearsal failed"; tail -20 "$OUT/reh2.log"; exit 4; }
   tail -1 "$OUT/reh2.log" | cut -c1-600
 fi

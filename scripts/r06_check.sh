@@ -21,7 +21,7 @@ if [ "${SKIP_STAMPS:-0}" != "1" ]; then
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
   echo "== bench (default)"
-  timeout -k 10 600 python bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 3; }
+  timeout -k 10 600 python bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 3; }
   tail -1 "$OUT/bench.log" | cut -c1-400
 fi
 if [ "${SHARES:-1}" = "1" ]; then

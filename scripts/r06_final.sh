@@ -17,5 +17,5 @@ if [ "${SHARES_5M:-1}" = "1" ]; then
   tail -4 "$OUT/rank_share.log" | cut -c1-200
 fi
 echo "== rehearsal: bench.py --gpus 2, both ranks on GPU 0, host transport"
-TPL_DEVICE=0 TPL_DIST_TRANSPORT=host timeout -k 10 700 python bench.py --gpus 2 --steps 3 --warmup 1 --child-timeout 650 > "$OUT/reh2.log" 2>&1 || { echo "rehearsal failed"; tail -20 "$OUT/reh2.log"; exit 8; }
+TPL_DEVICE=0 TPL_DIST_TRANSPORT=host timeout -k 10 700 python bench.py --full --gpus 2 --steps 3 --warmup 1 --child-timeout 650 > "$OUT/reh2.log" 2>&1 || { echo "rehearsal failed"; tail -20 "$OUT/reh2.log"; exit 8; }
 tail -1 "$OUT/reh2.log" | cut -c1-300

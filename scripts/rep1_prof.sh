@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 cd "$ROOT"
-timeout -k 10 400 python bench.py --gpus 1 --partition 1 --steps 5 --warmup 1 --parity 0 \
+timeout -k 10 400 python bench.py --full --gpus 1 --partition 1 --steps 5 --warmup 1 --parity 0 \
   > "$OUT/rep1_bench.log" 2>&1 || { echo "rep1 bench failed"; tail -20 "$OUT/rep1_bench.log"; exit 2; }
 tail -1 "$OUT/rep1_bench.log"
 cd /tmp && export TMPDIR=/tmp

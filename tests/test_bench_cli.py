@@ -19,6 +19,32 @@ def test_defaults():
     assert (a.gpus, a.steps, a.warmup, a.k) == (1, 5, 1, 500)
 
 
+def test_plain_run_switches_every_other_leg_off():
+    """Without --full only the timed solves run, whatever the legs' own switches say;
+    --full leaves every leg at its default (on)."""
+    legs = ("other_configs", "one_pass", "pcie", "scale_ref", "cpu_baseline", "single_ref",
+            "parity", "configs4", "replicas")
+    a = bench.parse(["--pcie", "1", "--steps", "7"])
+    assert a.full is False and a.dump_outputs is None
+    bench.plain_run(a)
+    assert a.headline_only == 1 and a.steps == 7
+    assert all(getattr(a, leg) == 0 for leg in legs)
+    f = bench.parse(["--full", "--dump-outputs", "d"])
+    assert f.full is True and f.dump_outputs == "d" and f.headline_only == 0
+    assert all(getattr(f, leg) == 1 for leg in legs)
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: DIR is created, each array lands as DIR/<name>.npy in float64."""
+    import numpy as np
+    x = np.linspace(-1.0, 1.0, 7)
+    d = tmp_path / "a" / "b"
+    bench.dump_outputs(str(d), x=x)
+    assert sorted(os.listdir(d)) == ["x.npy"]
+    got = np.load(d / "x.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, x)
+
+
 def test_launch_command_shape():
     cmd = bench.launch_command(["--gpus", "8", "--steps", "3", "--warmup", "1"], 8, 29555)
     assert cmd[:3] == [sys.executable, "-m", "torch.distributed.run"]
@@ -209,6 +235,10 @@ def test_multi_line():
     assert line["value"] == 90000.0 and line["partitioned_configs4"]["status"] == "failed"
     assert line["status"] == "partitioned_configs4: failed" and not line["parity"]["all_ok"]
     assert bench.failed_line(4, "failed", "x")["value"] is None
+    # a plain run (no --full) checks nothing: the line carries no parity block at all
+    plain = bench.multi_line(head, 4, argparse.Namespace(steps=5, warmup=1, k=500, full=False))
+    assert "parity" not in plain and plain["value"] == 90000.0
+    assert bench.sub_phase_failed(plain, "report", "failed", "x")["status"] == "report: failed"
 
 
 _RANK = r"""
