@@ -1,8 +1,9 @@
 // sanitize_driver.cpp — the engine's host C++ (the .dmx/.qfc loader, the f(T_k) solvers,
-// the SpMV layout builder) built with -fsanitize=address,undefined on the CPU and driven
-// over the committed fixture, malformed and random inputs (sanitizers on
-// host code; tpl_loader.cpp parses untrusted files). Any sanitizer report aborts the run;
-// the layout checks also verify that every nonzero lands exactly once in the layout.
+// the SpMV layout builder, the partition planner) built with -fsanitize=address,undefined
+// on the CPU and driven over the committed fixture, malformed and random inputs (SURVEY.md
+// §5: sanitizers on host code; tpl_loader.cpp parses untrusted files). Any sanitizer report aborts the run;
+// the layout checks also verify that every nonzero lands exactly once in the layout, the
+// planner checks that every rank's rows, local CSR and halo plan are the input's.
 //
 //   sanitize_driver <netgen-5000-3.dmx> <qfc> <scratch dir>
 #include <algorithm>
@@ -18,6 +19,7 @@
 #include "tpl.h"
 #include "tpl_internal.h"
 #include "tpl_layout.h"
+#include "tpl_partition.h"
 
 static int g_fail = 0;
 #define CHECK(cond, ...)                                \
@@ -325,6 +327,177 @@ static void locality_abi_checks() {
   CHECK(accepted > 50, "only %d valid mutations", accepted);
 }
 
+// ---- the partition planner (tpl_partition.h), called directly as the layout builder is
+static bool same_plan(const tpl::RankPlan& a, const tpl::RankPlan& b) {
+  return a.n == b.n && a.nnz == b.nnz && a.n_glob == b.n_glob && a.starts == b.starts &&
+         a.hybrid == b.hybrid && a.ns_local == b.ns_local && a.g2l == b.g2l &&
+         a.local_rows == b.local_rows && a.local_order == b.local_order && a.nch == b.nch &&
+         a.g2s == b.g2s && a.halo == b.halo && a.hH == b.hH && a.halo_send == b.halo_send &&
+         a.halo_map == b.halo_map && a.h_rowptr == b.h_rowptr && a.h_col == b.h_col &&
+         a.h_val == b.h_val && a.long_from == b.long_from && a.elem_rows == b.elem_rows;
+}
+
+// Row blocks (halo or not) of R ranks: the blocks tile 0..n, each rank's CSR is the slice of
+// the input, and the halo plan is the brute-force one.
+static void row_block_checks(const char* tag, int R, int64_t n, const int64_t* rp, const int32_t* col,
+                             const double* val, bool halo) {
+  const tpl::RowSplit s = tpl::split_rows(R, n, nullptr, rp, col, true, halo);
+  const std::vector<int64_t>& st = s.starts;
+  bool tiles = (int)st.size() == R + 1 && st[0] == 0 && st[R] == n;
+  for (int r = 0; tiles && r < R; ++r) tiles = st[r + 1] > st[r];
+  CHECK(tiles, "%s R=%d: blocks do not tile 0..n", tag, R);
+  if (!tiles) return;
+  // referenced[c]: some row outside c's block references column c
+  std::vector<char> referenced(n, 0);
+  for (int r = 0; r < R; ++r)
+    for (int64_t q = rp[st[r]]; q < rp[st[r + 1]]; ++q)
+      if (col[q] < st[r] || col[q] >= st[r + 1]) referenced[col[q]] = 1;
+  int64_t H = 0;
+  for (int r = 0; r < R; ++r)
+    H = std::max<int64_t>(H, std::count(referenced.begin() + st[r], referenced.begin() + st[r + 1], 1));
+  for (int me = 0; me < R; ++me) {
+    const tpl::RankPlan p = tpl::materialise(s, me, rp, col, val);
+    const int64_t r0 = st[me], r1 = st[me + 1];
+    bool slice = p.n == r1 - r0 && p.n_glob == n && p.nnz == rp[r1] - rp[r0] && p.starts == st &&
+                 (int64_t)p.h_rowptr.size() == p.n + 1 && (int64_t)p.h_col.size() == p.nnz &&
+                 (int64_t)p.h_val.size() == p.nnz && !p.hybrid && p.halo == halo;
+    for (int64_t i = 0; slice && i <= p.n; ++i) slice = p.h_rowptr[i] == rp[r0 + i] - rp[r0];
+    for (int64_t q = 0; slice && q < p.nnz; ++q)
+      slice = p.h_col[q] == col[rp[r0] + q] && p.h_val[q] == val[rp[r0] + q];
+    CHECK(slice, "%s R=%d rank %d: CSR is not the slice of the input", tag, R, me);
+    if (!halo) continue;
+    CHECK(p.hH == H, "%s R=%d rank %d: hH %lld, brute force %lld", tag, R, me, (long long)p.hH,
+          (long long)H);
+    const int64_t ld = tpl::padded_stride(p.n);
+    bool map_ok = (int64_t)p.halo_map.size() == n;
+    std::map<int32_t, int32_t> remote;  // position -> column
+    for (int64_t q = rp[r0]; map_ok && q < rp[r1]; ++q) {
+      const int32_t c = col[q], m = p.halo_map[c];
+      map_ok = m >= 0 && m < ld + (int64_t)R * p.hH;
+      if (c >= r0 && c < r1) map_ok = map_ok && m == c - r0;
+      else map_ok = map_ok && m >= ld && remote.emplace(m, c).first->second == c;
+    }
+    CHECK(map_ok, "%s R=%d rank %d: halo_map", tag, R, me);
+    std::vector<int32_t> send;
+    for (int64_t c = r0; c < r1; ++c)
+      if (referenced[c]) send.push_back((int32_t)(c - r0));
+    CHECK(p.halo_send == send, "%s R=%d rank %d: halo_send", tag, R, me);
+  }
+}
+
+// Replicated long rows: every short row on one rank and every long row on all, every
+// nonzero exactly once over the ranks, local indices consistent, counts agreed.
+static void replicated_checks(const char* tag, const tpl::ReplicatedSplit& s, int R, int64_t n,
+                              const int64_t* rp, const int32_t* col, const double* val) {
+  std::vector<int> row_seen(n, 0), nz_seen(rp[n], 0);
+  std::vector<int32_t> nch, g2s;
+  for (int me = 0; me < R; ++me) {
+    const tpl::RankPlan p = tpl::materialise(s, me, rp, col, val);
+    bool ok = p.hybrid && (int64_t)p.local_rows.size() == p.n && (int64_t)p.g2l.size() == n &&
+              (int64_t)p.h_rowptr.size() == p.n + 1 && p.long_from == p.ns_local &&
+              p.nnz == (int64_t)p.h_col.size() && p.h_val.size() == p.h_col.size() &&
+              std::count_if(p.g2l.begin(), p.g2l.end(), [](int32_t l) { return l >= 0; }) == p.n;
+    for (int64_t i = 0; ok && i < p.n; ++i) {
+      const int64_t g = p.local_rows[i];
+      ok = g >= 0 && g < n && p.g2l[g] == i && (s.lidx[g] >= 0) == (i >= p.ns_local);
+      if (!ok) break;
+      ++row_seen[g];
+      for (int32_t q = p.h_rowptr[i]; ok && q < p.h_rowptr[i + 1]; ++q) {
+        const int32_t lc = p.h_col[q];
+        ok = lc >= 0 && lc < p.n && (q == p.h_rowptr[i] || lc > p.h_col[q - 1]);
+        if (!ok) break;
+        // the input entry (g, global column) this local entry is
+        const int32_t* at = std::lower_bound(col + rp[g], col + rp[g + 1], (int32_t)p.local_rows[lc]);
+        ok = at < col + rp[g + 1] && *at == p.local_rows[lc] && val[at - col] == p.h_val[q];
+        if (ok) ++nz_seen[at - col];
+      }
+    }
+    CHECK(ok, "%s R=%d rank %d: replicated plan", tag, R, me);
+    if (me == 0) nch = p.nch, g2s = p.g2s;
+    CHECK((int)p.nch.size() == R && p.nch == nch && p.g2s == g2s, "%s R=%d rank %d: nch / g2s differ",
+          tag, R, me);
+  }
+  bool rows_ok = true, nz_ok = true;
+  for (int64_t i = 0; i < n; ++i) rows_ok = rows_ok && row_seen[i] == (s.lidx[i] >= 0 ? R : 1);
+  for (int64_t q = 0; q < rp[n]; ++q) nz_ok = nz_ok && nz_seen[q] == 1;
+  CHECK(rows_ok, "%s R=%d: short rows once, long rows on every rank", tag, R);
+  CHECK(nz_ok, "%s R=%d: every nonzero exactly once over the ranks", tag, R);
+}
+
+// One matrix at every R and rank; counts the feasible / infeasible replicated splits.
+static void planner_case(const char* tag, int64_t n, const std::vector<int64_t>& rp,
+                         const std::vector<int32_t>& col, const std::vector<double>& val,
+                         int* feasible, int* infeasible) {
+  try {
+    for (int R : {1, 2, 3, 4, 8}) {
+      if (n < R) continue;
+      row_block_checks(tag, R, n, rp.data(), col.data(), val.data(), false);
+      row_block_checks(tag, R, n, rp.data(), col.data(), val.data(), true);
+      const tpl::ReplicatedSplit rs = tpl::split_replicated(R, n, rp.data(), col.data());
+      ++*(rs.feasible() ? feasible : infeasible);
+      if (rs.feasible()) replicated_checks(tag, rs, R, n, rp.data(), col.data(), val.data());
+      // choose_partition: the mode the splits give separately, and the explicit path's plans
+      const tpl::RowSplit hs = tpl::split_rows(R, n, nullptr, rp.data(), col.data(), true, true);
+      int64_t widest = 0;
+      for (int r = 0; r < R; ++r) widest = std::max(widest, hs.starts[r + 1] - hs.starts[r]);
+      const int want = rs.feasible() ? TPL_PLAN_REPLICATED : 2 * hs.H <= widest ? TPL_PLAN_HALO : TPL_PLAN_ROWS;
+      const tpl::PartitionChoice c = tpl::choose_partition(n, rp.data(), col.data(), R);
+      CHECK(c.mode == want, "%s R=%d: choose_partition %d, the splits say %d", tag, R, c.mode, want);
+      if (c.mode != want) continue;
+      const tpl::RowSplit ps = tpl::split_rows(R, n, nullptr, rp.data(), col.data(), true, false);
+      for (int me = 0; me < R; ++me) {
+        const tpl::RankPlan got = want == TPL_PLAN_REPLICATED
+                                      ? tpl::materialise(c.rep, me, rp.data(), col.data(), val.data())
+                                      : tpl::materialise(c.rows, me, rp.data(), col.data(), val.data());
+        const tpl::RankPlan exp =
+            want == TPL_PLAN_REPLICATED ? tpl::materialise(rs, me, rp.data(), col.data(), val.data())
+                                        : tpl::materialise(want == TPL_PLAN_HALO ? hs : ps, me, rp.data(),
+                                                           col.data(), val.data());
+        CHECK(same_plan(got, exp), "%s R=%d rank %d: the chosen split's plan differs", tag, R, me);
+      }
+    }
+  } catch (const tpl::Error& e) {
+    std::printf("FAIL planner %s: %s\n", tag, e.msg.c_str());
+    ++g_fail;
+  }
+}
+
+static void planner_checks(const char* dmx, const char* qfc) {
+  int feas = 0, infeas = 0;
+  tpl_csr_host A{};
+  CHECK(tpl_load_kkt_system(dmx, qfc, &A) == TPL_OK, "fixture: %s", tpl_last_error());
+  planner_case("kkt5k", A.n, std::vector<int64_t>(A.row_ptr, A.row_ptr + A.n + 1),
+               std::vector<int32_t>(A.col_idx, A.col_idx + A.nnz),
+               std::vector<double>(A.vals, A.vals + A.nnz), &feas, &infeas);
+  CHECK(feas == 5 && infeas == 0, "the KKT fixture takes replicated long rows at every R");
+  tpl_csr_host_free(&A);
+  {  // tridiagonal band, n = 64
+    std::vector<int64_t> rp(1, 0);
+    std::vector<int32_t> col;
+    std::vector<double> val;
+    for (int32_t i = 0; i < 64; ++i) {
+      for (int32_t j = std::max(i - 1, 0); j <= std::min(i + 1, 63); ++j) {
+        col.push_back(j);
+        val.push_back(i == j ? 4.0 : -1.0 - 0.01 * std::min(i, j));
+      }
+      rp.push_back((int64_t)col.size());
+    }
+    planner_case("band64", 64, rp, col, val, &feas, &infeas);
+  }
+  feas = infeas = 0;
+  std::mt19937_64 rng(2024);
+  for (int it = 0; it < 30; ++it) {
+    const int64_t n = 8 + (int64_t)(rng() % 193);
+    std::vector<int32_t> rp32, col;
+    std::vector<double> val;
+    random_csr(n, 1 + (int)(rng() % 3), (int)(n / 2 + rng() % n), rng(), rp32, col, val);
+    const std::string tag = "random" + std::to_string(it);
+    planner_case(tag.c_str(), n, std::vector<int64_t>(rp32.begin(), rp32.end()), col, val, &feas, &infeas);
+  }
+  CHECK(feas > 0 && infeas > 0, "random patterns: %d feasible, %d infeasible replicated splits", feas,
+        infeas);
+}
+
 int main(int argc, char** argv) {
   if (argc < 4) {
     std::printf("usage: sanitize_driver <dmx> <qfc> <scratch dir>\n");
@@ -333,6 +506,7 @@ int main(int argc, char** argv) {
   loader_checks(argv[1], argv[2], argv[3]);
   ftk_checks();
   layout_checks();
+  planner_checks(argv[1], argv[2]);
   locality_abi_checks();
   std::printf("%s (%d failures)\n", g_fail ? "FAILED" : "OK", g_fail);
   return g_fail ? 1 : 0;

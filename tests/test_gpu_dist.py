@@ -269,3 +269,56 @@ def test_halo_create_rejects_bad_input():
         assert create(6, [0, 3, 6])[0] == _lib.TPL_OK
     finally:
         _lib.tpl_dist_destroy(d.value)
+
+
+def test_failed_rebuild_leaves_operator_intact(kkt_tmp):
+    """A setter whose layout rebuild is refused leaves a working operator. On a replicated
+    operator the ranks have agreed on every rank's element-wise block count, so halving
+    max_g2 is refused (TPL_ERR_UNSUPPORTED) after the new layout was built: the operator must
+    still hold its old layout, parameters and device buffers — checked on the host before
+    anything runs on the device again — and then solve to the same bits. One rank over the
+    host transport, the callback copying its part: eager launches, no torch.distributed."""
+    import ctypes
+    import types
+    from ctypes import byref, c_void_p
+
+    import tpl_amd
+    from tpl_amd import _lib
+    from tpl_amd.dist import DistHipCsrOp
+    from tpl_amd.error import TplError
+
+    def allgather(send, recv, nbytes, _user):
+        ctypes.memmove(recv, send, nbytes)
+        return 0
+
+    cb = _lib.ALLGATHER_FN(allgather)
+    d = c_void_p()
+    assert _lib.tpl_dist_create_host(0, 0, 1, cb, None, byref(d)) == _lib.TPL_OK
+    op = None
+    try:
+        a = load_kkt(5000, kkt_tmp).a
+        op = DistHipCsrOp(a, types.SimpleNamespace(handle=d.value, device=0, rank=0, world=1),
+                          mode="replicated")
+        assert op.mode == "replicated" and not op.uses_graphs
+        bl = op.local(harness_b(a))
+        x0 = tpl_amd.lanczos_two_pass(op, bl, 20, "inv")
+        sched, flags, nbytes = op.schedule(), op.flags(), op.device_bytes()
+        assert sched["G2"] >= 2
+        with pytest.raises(TplError) as e:
+            op.set_schedule(max_g2=sched["G2"] // 2)
+        assert e.value.status == _lib.TPL_ERR_UNSUPPORTED
+        assert str(e.value) == ("replicated partition: the element-wise blocks must stay those "
+                                "every rank computed from the split")
+        after = op.schedule()
+        assert after.keys() == sched.keys()
+        for key, v in sched.items():
+            assert np.array_equal(after[key], v) and (after[key] is None) == (v is None), key
+        assert op.flags() == flags
+        assert op.device_bytes() == nbytes
+        op.set_schedule(0, 0)  # no parameter of the refused call stayed behind
+        x1 = tpl_amd.lanczos_two_pass(op, bl, 20, "inv")
+        assert np.array_equal(x1, x0)
+    finally:
+        if op is not None:
+            op.close()
+        _lib.tpl_dist_destroy(d.value)

@@ -120,6 +120,11 @@ int32_t short_row_threshold(int64_t n, const std::vector<int32_t>& rp, int reque
 // of a node's arcs hit lines their neighbours have just fetched.
 std::vector<int32_t> locality_order(int64_t n, const std::vector<int32_t>& rp,
                                     const std::vector<int32_t>& col, const SchedParams& sp);
+// Locality order, auto mode: on up to this many rows. Measured k_p2_spmv (KKT, D = 0;
+// profiles/r02_order_lab.txt): 500k arcs 8.76 -> 6.91 us, 1M arcs 12.8 -> 11.8 us,
+// 50k / 5k arcs flat; 2M arcs 20.5 -> 21.8 us and 5M arcs 54 -> 58 us (the gathered
+// vector, 16-40 MB, no longer fits the XCDs' L2s).
+constexpr int64_t kReorderAutoMaxRows = 1 << 20;
 
 // The locality order's sort of short rows (shared by locality_order and the replicated
 // partition's per-rank order, tpl_dist_op_create_replicated): `rows` (indices into the

@@ -25,6 +25,7 @@
 #include "tpl_device.h"
 #include "tpl_internal.h"
 #include "tpl_layout.h"
+#include "tpl_partition.h"
 
 #ifndef TPL_LAB
 #define TPL_LAB 0  // lab builds only (scripts/build_variants.sh): runtime layout knobs
@@ -158,66 +159,41 @@ constexpr size_t kDevFtkAutoK = 500;
 // 4 k + 4 doubles of dynamic LDS plus 8.2 KB of static arrays: 65.8 KB at this k, which
 // gfx950's 160 KiB of LDS per workgroup holds (a 64 KiB part would need k <= 1790).
 constexpr size_t kDevExpMaxK = 1800;
-// Which built-in f(T_k) a one-graph solve evaluates on the device.
-enum DevF { kDevInv = 0, kDevExp = 1 };
-// Locality order, auto mode: on up to this many rows. Measured k_p2_spmv (KKT, D = 0;
-// profiles/r02_order_lab.txt): 500k arcs 8.76 -> 6.91 us, 1M arcs 12.8 -> 11.8 us,
-// 50k / 5k arcs flat; 2M arcs 20.5 -> 21.8 us and 5M arcs 54 -> 58 us (the gathered
-// vector, 16-40 MB, no longer fits the XCDs' L2s).
-constexpr int64_t kReorderAutoMaxRows = 1 << 20;
+// Which built-in f(T_k) a solve evaluates on the device (kDevHost: none, f runs on the host).
+enum DevF { kDevHost = -1, kDevInv = 0, kDevExp = 1 };
+
+// The device buffers of a Layout (and of its row order): rebuild_schedule replaces the set.
+struct LayoutBufs {
+  void *d_scol = nullptr, *d_sval = nullptr, *d_bcol = nullptr, *d_bval = nullptr;
+  int32_t *d_srows = nullptr, *d_scbase = nullptr, *d_cbase = nullptr, *d_cwidth = nullptr;
+  int32_t *d_bcbase = nullptr, *d_bhdr = nullptr;
+  BinSeg* d_bseg = nullptr;
+  double* d_P = nullptr;
+  unsigned int* d_Pcnt = nullptr;
+  int32_t *d_perm = nullptr, *d_iperm = nullptr;  // locality order (empty perm: nullptr)
+  double* d_stage = nullptr;        // one host-order vector (host uploads / downloads)
+};
 }
 
 struct tpl_op_s {
-  tpl_ctx_s* ctx = nullptr;
   int device = 0;
   hipStream_t stream = nullptr;
-  int64_t n = 0, nnz = 0;           // this operator's rows (the rank's block) and nonzeros
-  // row partition (tpl_dist_op_create_csr); single GPU: dist == nullptr, n_glob == n
+  // this operator's rows, their CSR (h_rowptr / h_col / h_val keep the caller's order)
+  // and its place in the partition; single GPU: dist == nullptr, n_glob == n
+  RankPlan part;
   tpl_dist_s* dist = nullptr;
-  int64_t n_glob = 0;
-  std::vector<int64_t> starts;
   bool eager = false;               // launch without graphs (host transport / no capture)
-  // replicated-long-row partition ("hybrid"): local vector = [own short rows | all long
-  // rows]; g2l maps global rows/columns to local indices (-1: not local), local_rows back
-  bool hybrid = false;
-  int64_t ns_local = 0;
-  std::vector<int32_t> g2l;
-  std::vector<int64_t> local_rows;
   double* d_yall = nullptr;         // nranks x y_ld1 (pass one: long-row partials + the
                                     // rank's short-chunk alpha partials, all-gathered
                                     // together); pass two: nranks x (n_long + 1)
   int32_t y_ld1 = 0;                // n_long + the most chunks of any rank
-  std::vector<int32_t> nch;         // chunks (alpha partials) of every rank
-  std::vector<int32_t> g2s;         // norm partials (element-wise blocks) of every rank
   int32_t pb_ld = 0;                // > 0: every rank's norm partials all-gathered (CsrDev::pb_ld)
   double* d_pball = nullptr;        // [nranks x pb_ld] gathered norm partials (pb_ld > 0)
   int32_t* d_nch = nullptr;
-  // halo-exchange row blocks (tpl_dist_op_create_halo): the gathered vector is
-  // [own block (ld) | nranks x hH halo slots]; rank q's slot holds the hH_q <= hH rows of
-  // its block that some other rank's rows reference (halo_send: their local indices),
-  // packed before each all-gather; halo_map: global column -> device position
-  bool halo = false;
-  int64_t hH = 0;
-  std::vector<int32_t> halo_send, halo_map;
   int32_t* d_halo_send = nullptr;
-  std::vector<int32_t> h_rowptr;
-  std::vector<int32_t> h_col;
-  std::vector<double> h_val;
   SchedParams sp;
   Layout lay;
-  void* d_bcol = nullptr;
-  int32_t* d_bcbase = nullptr;
-  int32_t* d_bhdr = nullptr;
-  int32_t* d_scbase = nullptr;
-  void* d_bval = nullptr;
-  BinSeg* d_bseg = nullptr;
-  double* d_P = nullptr;
-  unsigned int* d_Pcnt = nullptr;
-  int32_t* d_srows = nullptr;
-  void* d_scol = nullptr;
-  void* d_sval = nullptr;
-  int32_t* d_cbase = nullptr;
-  int32_t* d_cwidth = nullptr;
+  LayoutBufs bufs;
   // vectors: b, R0..R2, W, x, V2_0..V2_2, tmp (n each, padded)
   double* d_vecs = nullptr;
   int64_t ld = 0;
@@ -247,13 +223,8 @@ struct tpl_op_s {
   int64_t reorth_second = 0;        // second Gram-Schmidt passes of the last reorth solve
   // locality order (single GPU, tpl_op_set_reorder): the device works on P A P^T; vectors
   // cross the boundary through a gather (internal i <- caller's perm[i], back via iperm).
-  // h_rowptr / h_col / h_val keep the caller's order.
   int reorder = 2;                  // 0 off, 1 on, 2 auto (n <= kReorderAutoMaxRows)
-  bool local_order = false;         // replicated partition: own short rows in locality order
   std::vector<int32_t> perm, iperm;
-  int32_t* d_perm = nullptr;
-  int32_t* d_iperm = nullptr;
-  double* d_stage = nullptr;        // one host-order vector (host uploads / downloads)
   double* d_Vext = nullptr;         // the callback's V_k view in the caller's order
   size_t vext_cols = 0;
   hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -282,22 +253,22 @@ int long_epi_blocks(const tpl_op_s* op) {
 CsrDev csr_dev(const tpl_op_s* op, bool pass1 = false) {
   const Layout& L = op->lay;
   CsrDev A;
-  A.srows = op->d_srows;
-  A.s_col = op->d_scol;
-  A.s_val = op->d_sval;
+  A.srows = op->bufs.d_srows;
+  A.s_col = op->bufs.d_scol;
+  A.s_val = op->bufs.d_sval;
   A.val_i8 = L.val_i8 ? 1 : 0;
   A.s_col16 = L.s_col16 ? 1 : 0;
   A.b_col16 = L.b_col16 ? 1 : 0;
-  A.s_cbase = op->d_scbase;
-  A.b_cbase = op->d_bcbase;
-  A.c_base = op->d_cbase;
-  A.c_width = op->d_cwidth;
-  A.b_col = op->d_bcol;
-  A.b_val = op->d_bval;
-  A.b_seg = op->d_bseg;
-  A.b_hdr = op->d_bhdr;
-  A.P = op->d_P;
-  A.Pcnt = op->d_Pcnt;
+  A.s_cbase = op->bufs.d_scbase;
+  A.b_cbase = op->bufs.d_bcbase;
+  A.c_base = op->bufs.d_cbase;
+  A.c_width = op->bufs.d_cwidth;
+  A.b_col = op->bufs.d_bcol;
+  A.b_val = op->bufs.d_bval;
+  A.b_seg = op->bufs.d_bseg;
+  A.b_hdr = op->bufs.d_bhdr;
+  A.P = op->bufs.d_P;
+  A.Pcnt = op->bufs.d_Pcnt;
   A.s_width = L.s_width;
   A.s_identity = L.s_identity;
   A.n_short = (int32_t)L.srows.size();
@@ -308,17 +279,17 @@ CsrDev csr_dev(const tpl_op_s* op, bool pass1 = false) {
   A.n_slice_blocks = L.nslices * L.M;
   A.G2 = L.G2;
   A.NA = A.n_chunks + A.n_long;
-  A.NA_r = op->dist ? op->dist->nranks + (op->hybrid ? long_epi_blocks(op) : 0) : A.NA;
+  A.NA_r = op->dist ? op->dist->nranks + (op->part.hybrid ? long_epi_blocks(op) : 0) : A.NA;
   A.G2_r = op->dist ? op->dist->nranks : A.G2;
   A.pb_ld = op->pb_ld;
-  A.long_defer = op->hybrid ? 1 : 0;
-  A.y_ld = pass1 && op->hybrid ? op->y_ld1 : (int32_t)L.lrows.size() + 1;
-  A.ypart = op->hybrid ? op->d_yall + (size_t)op->dist->rank * A.y_ld : nullptr;
+  A.long_defer = op->part.hybrid ? 1 : 0;
+  A.y_ld = pass1 && op->part.hybrid ? op->y_ld1 : (int32_t)L.lrows.size() + 1;
+  A.ypart = op->part.hybrid ? op->d_yall + (size_t)op->dist->rank * A.y_ld : nullptr;
   A.nch = op->d_nch;
-  A.norm_n = op->hybrid && op->dist->rank != 0 ? op->ns_local : op->n;
+  A.norm_n = op->part.hybrid && op->dist->rank != 0 ? op->part.ns_local : op->part.n;
   A.s_win = L.s_win;
   A.s_win_max = L.s_win_max;
-  A.n = op->n;
+  A.n = op->part.n;
   A.E = L.E;
   return A;
 }
@@ -350,31 +321,86 @@ void upload(tpl_op_s* op, T** dst, const std::vector<T>& src) {
   HIPCHK(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
 }
 
-void rebuild_schedule(tpl_op_s* op) {
+void free_bufs(tpl_op_s* op, LayoutBufs& b) {
+  dev_free(op, b.d_scol), dev_free(op, b.d_sval), dev_free(op, b.d_bcol), dev_free(op, b.d_bval);
+  dev_free(op, b.d_srows), dev_free(op, b.d_scbase), dev_free(op, b.d_cbase);
+  dev_free(op, b.d_cwidth), dev_free(op, b.d_bcbase), dev_free(op, b.d_bhdr);
+  dev_free(op, b.d_bseg), dev_free(op, b.d_P), dev_free(op, b.d_Pcnt);
+  dev_free(op, b.d_perm), dev_free(op, b.d_iperm), dev_free(op, b.d_stage);
+}
+
+// A layout (and its row order) into a fresh set of device buffers.
+void upload_layout(tpl_op_s* op, const Layout& L, const std::vector<int32_t>& perm,
+                   const std::vector<int32_t>& iperm, LayoutBufs& nb) {
+  upload(op, &nb.d_perm, perm);
+  upload(op, &nb.d_iperm, iperm);
+  if (!perm.empty()) dev_alloc(op, &nb.d_stage, perm.size() * sizeof(double));
+  upload(op, &nb.d_srows, L.srows);
+  // entries in the device order (tpl_device.h kPackedEntries; positions unchanged)
+  const bool pack_s = packed_chunk_width(L.s_width);
+  auto sidx = [&](int64_t i) { return pack_s ? packed_chunk_index(i, L.s_width) : i; };
+  auto bidx = [&](int64_t i) { return kPackedEntries ? packed_bin_index(i, L.bin_cap) : i; };
+  if (L.s_col16)
+    upload(op, reinterpret_cast<uint16_t**>(&nb.d_scol), to_device_order(L.s_col16v, sidx));
+  else
+    upload(op, reinterpret_cast<int32_t**>(&nb.d_scol), to_device_order(L.s_col, sidx));
+  upload(op, &nb.d_scbase, L.s_cbase);
+  if (L.val_i8)
+    upload(op, reinterpret_cast<int8_t**>(&nb.d_sval), to_device_order(L.s_val8, sidx));
+  else
+    upload(op, reinterpret_cast<double**>(&nb.d_sval), to_device_order(L.s_val, sidx));
+  upload(op, &nb.d_cbase, L.c_base);
+  upload(op, &nb.d_cwidth, L.c_width);
+  if (L.b_col16)
+    upload(op, reinterpret_cast<uint16_t**>(&nb.d_bcol), to_device_order(L.b_col16v, bidx));
+  else
+    upload(op, reinterpret_cast<int32_t**>(&nb.d_bcol), to_device_order(L.b_col, bidx));
+  upload(op, &nb.d_bcbase, L.b_cbase);
+  if (L.val_i8)
+    upload(op, reinterpret_cast<int8_t**>(&nb.d_bval), to_device_order(L.b_val8, bidx));
+  else
+    upload(op, reinterpret_cast<double**>(&nb.d_bval), to_device_order(L.b_val, bidx));
+  upload(op, &nb.d_bseg, L.b_seg);
+  upload(op, &nb.d_bhdr, L.b_hdr);
+  // piece slots, and the arrival counters of the sliced long rows (zero; each wraps at
+  // its row's packed-piece count, BinSeg::pad + 1, so it runs on across launches)
+  upload(op, &nb.d_P, std::vector<double>(std::max<size_t>(L.lrows.size() * kSlotStride, 1), 0.0));
+  upload(op, &nb.d_Pcnt,
+         std::vector<unsigned int>(std::max<size_t>(L.lrows.size() * kCntStride, 1), 0u));
+}
+
+// The operator's row order, Layout and their device buffers under the schedule parameters
+// `cand` and the order mode `reorder`. Everything is built aside and swapped into the
+// operator only once it is complete, `cand` and `reorder` with it: when anything throws
+// (a layout the kernels or the partition cannot hold, device memory), the operator keeps
+// its layout, buffers, graphs, state and parameters, and what was allocated on the way is
+// freed. The price: while both sets exist a rebuild's peak device memory is one layout's
+// worth higher (init_op's first build has no old set).
+void rebuild_schedule(tpl_op_s* op, const SchedParams& cand, int reorder) {
   ColMap cmap;
-  if (op->halo) {
-    cmap.table = &op->halo_map;
-  } else if (op->dist && !op->hybrid) {
-    cmap.starts = &op->starts;
+  const RankPlan& part = op->part;
+  if (part.halo) {
+    cmap.table = &part.halo_map;
+  } else if (op->dist && !part.hybrid) {
+    cmap.starts = &part.starts;
     cmap.ld = op->ld;
   }
-  op->perm.clear();
-  op->iperm.clear();
-  const bool want = op->reorder == 1 || (op->reorder == 2 && op->n <= kReorderAutoMaxRows);
-  if (want && !op->dist) op->perm = locality_order(op->n, op->h_rowptr, op->h_col, op->sp);
+  std::vector<int32_t> perm, iperm;
+  const bool want = reorder == 1 || (reorder == 2 && part.n <= kReorderAutoMaxRows);
+  if (want && !op->dist) perm = locality_order(part.n, part.h_rowptr, part.h_col, cand);
   std::vector<int32_t> prp, pcol;
   std::vector<double> pval;
-  if (!op->perm.empty()) {
-    op->iperm.resize(op->n);
-    for (int64_t i = 0; i < op->n; ++i) op->iperm[op->perm[i]] = (int32_t)i;
-    permute_csr(op->n, op->h_rowptr, op->h_col, op->h_val, op->perm, op->iperm, prp, pcol, pval);
+  const bool p = !perm.empty();
+  if (p) {
+    iperm.resize(part.n);
+    for (int64_t i = 0; i < part.n; ++i) iperm[perm[i]] = (int32_t)i;
+    permute_csr(part.n, part.h_rowptr, part.h_col, part.h_val, perm, iperm, prp, pcol, pval);
   }
-  const bool p = !op->perm.empty();
   // In the locality order a chunk's rows share their hub columns, so its gathers hit
   // few lines and the LDS window costs more than it saves (measured +0.4 us per SpMV at
   // 500k): window only in the caller's order.
-  SchedParams sp = op->sp;
-  sp.window = !p && !op->local_order;
+  SchedParams sp = cand;
+  sp.window = !p && !part.local_order;
 #if TPL_LAB
   // layout knobs of the lab builds (scripts/build_variants.sh -DTPL_LAB=1), never in the
   // product library: the measured alternatives of DESIGN.md §3/§4
@@ -393,53 +419,31 @@ void rebuild_schedule(tpl_op_s* op) {
 #endif
   // slice bounds over global columns — or, replicated-long-row partition, over this
   // rank's local columns (its CSR is stored in local indices)
-  op->lay = build_layout(op->n, op->hybrid ? op->n : op->n_glob, p ? prp : op->h_rowptr,
-                         p ? pcol : op->h_col, p ? pval : op->h_val, sp, cmap);
+  Layout L = build_layout(part.n, part.hybrid ? part.n : part.n_glob, p ? prp : part.h_rowptr,
+                          p ? pcol : part.h_col, p ? pval : part.h_val, sp, cmap);
   // the replicated partition's ranks agree on every rank's element-wise block count (the
   // gathered norm partials, the alpha partial counts): a layout that changed it is refused
-  if (op->hybrid && !op->g2s.empty() && op->lay.G2 != op->g2s[op->dist->rank])
+  if (part.hybrid && !part.g2s.empty() && L.G2 != part.g2s[op->dist->rank])
     fail(TPL_ERR_UNSUPPORTED, "replicated partition: the element-wise blocks must stay those "
                               "every rank computed from the split");
-  if (op->plan_only) return;  // tpl_plan_create: the layout is all a plan holds
-  const Layout& L = op->lay;
-  upload(op, &op->d_perm, op->perm);
-  upload(op, &op->d_iperm, op->iperm);
-  dev_free(op, op->d_stage);
+  LayoutBufs nb;  // the new set; after the swap below, the old one
+  try {
+    if (!op->plan_only) upload_layout(op, L, perm, iperm, nb);  // a plan holds the layout only
+  } catch (...) {
+    free_bufs(op, nb);
+    throw;
+  }
+  // commit: nothing below throws
+  op->sp = cand;
+  op->reorder = reorder;
+  op->lay = std::move(L);
+  op->perm = std::move(perm);
+  op->iperm = std::move(iperm);
+  if (op->plan_only) return;
+  std::swap(op->bufs, nb);
+  free_bufs(op, nb);
   dev_free(op, op->d_Vext);
   op->vext_cols = 0;
-  if (p) dev_alloc(op, &op->d_stage, (size_t)op->n * sizeof(double));
-  upload(op, &op->d_srows, L.srows);
-  // entries in the device order (tpl_device.h kPackedEntries; positions unchanged)
-  const bool pack_s = packed_chunk_width(L.s_width);
-  auto sidx = [&](int64_t i) { return pack_s ? packed_chunk_index(i, L.s_width) : i; };
-  auto bidx = [&](int64_t i) { return kPackedEntries ? packed_bin_index(i, L.bin_cap) : i; };
-  if (L.s_col16)
-    upload(op, reinterpret_cast<uint16_t**>(&op->d_scol), to_device_order(L.s_col16v, sidx));
-  else
-    upload(op, reinterpret_cast<int32_t**>(&op->d_scol), to_device_order(L.s_col, sidx));
-  upload(op, &op->d_scbase, L.s_cbase);
-  if (L.val_i8)
-    upload(op, reinterpret_cast<int8_t**>(&op->d_sval), to_device_order(L.s_val8, sidx));
-  else
-    upload(op, reinterpret_cast<double**>(&op->d_sval), to_device_order(L.s_val, sidx));
-  upload(op, &op->d_cbase, L.c_base);
-  upload(op, &op->d_cwidth, L.c_width);
-  if (L.b_col16)
-    upload(op, reinterpret_cast<uint16_t**>(&op->d_bcol), to_device_order(L.b_col16v, bidx));
-  else
-    upload(op, reinterpret_cast<int32_t**>(&op->d_bcol), to_device_order(L.b_col, bidx));
-  upload(op, &op->d_bcbase, L.b_cbase);
-  if (L.val_i8)
-    upload(op, reinterpret_cast<int8_t**>(&op->d_bval), to_device_order(L.b_val8, bidx));
-  else
-    upload(op, reinterpret_cast<double**>(&op->d_bval), to_device_order(L.b_val, bidx));
-  upload(op, &op->d_bseg, L.b_seg);
-  upload(op, &op->d_bhdr, L.b_hdr);
-  // piece slots, and the arrival counters of the sliced long rows (zero; each wraps at
-  // its row's packed-piece count, BinSeg::pad + 1, so it runs on across launches)
-  upload(op, &op->d_P, std::vector<double>(std::max<size_t>(L.lrows.size() * kSlotStride, 1), 0.0));
-  upload(op, &op->d_Pcnt,
-         std::vector<unsigned int>(std::max<size_t>(L.lrows.size() * kCntStride, 1), 0u));
   drop_graphs(op);
   // partial buffers depend on the layout: force state reallocation
   op->kcap = 0;
@@ -481,7 +485,7 @@ void ensure_state(tpl_op_s* op, size_t k, bool reorth = false) {
     op->S.kcap = (int32_t)kc;
     // hybrid: the chunks' alpha partials go straight into this rank's pass-one segment of
     // the all-gather (k_long_epi_p1 reduces every rank's after the exchange)
-    if (op->hybrid)
+    if (op->part.hybrid)
       op->S.Pa = op->d_yall + (size_t)op->dist->rank * op->y_ld1 + op->lay.lrows.size();
     op->S.Pa_r = op->dist ? op->d_rsum : op->S.Pa;
     op->S.Pb_r = op->dist ? op->d_rsum + A.NA_r : op->S.Pb;
@@ -506,7 +510,7 @@ void ensure_basis(tpl_op_s* op, size_t cols) {
   op->d_V = nullptr;
   op->vcols = 0;
   const size_t c = std::max<size_t>(cols, 1);
-  dev_alloc(op, &op->d_V, (size_t)op->n * c * sizeof(double) + 64);
+  dev_alloc(op, &op->d_V, (size_t)op->part.n * c * sizeof(double) + 64);
   op->vcols = c;
 }
 
@@ -517,15 +521,15 @@ void set_device(const tpl_op_s* op) {
 }
 
 void check_b(const tpl_op_s* op, const double* b, int64_t b_len) {
-  if (!b && op->n > 0) fail(TPL_ERR_INVALID_ARGUMENT, "b is NULL");
-  if (b_len != op->n) fail_dimension(op->n, b_len);
+  if (!b && op->part.n > 0) fail(TPL_ERR_INVALID_ARGUMENT, "b is NULL");
+  if (b_len != op->part.n) fail_dimension(op->part.n, b_len);
 }
 
 // A caller-order vector into a device vector (internal order).
 void upload_vec(tpl_op_s* op, double* dst, const double* src, int mem) {
-  if (op->n == 0) return;
-  const size_t bytes = op->n * sizeof(double);
-  if (!op->d_perm) {
+  if (op->part.n == 0) return;
+  const size_t bytes = op->part.n * sizeof(double);
+  if (!op->bufs.d_perm) {
     HIPCHK(hipMemcpyAsync(dst, src, bytes,
                           mem == TPL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                           op->stream));
@@ -533,31 +537,33 @@ void upload_vec(tpl_op_s* op, double* dst, const double* src, int mem) {
   }
   const double* from = src;
   if (mem != TPL_MEM_DEVICE) {
-    HIPCHK(hipMemcpyAsync(op->d_stage, src, bytes, hipMemcpyHostToDevice, op->stream));
-    from = op->d_stage;
+    HIPCHK(hipMemcpyAsync(op->bufs.d_stage, src, bytes, hipMemcpyHostToDevice, op->stream));
+    from = op->bufs.d_stage;
   }
-  HIPCHK(launch::permute(op->n, 1, dst, op->n, from, op->n, op->d_perm, op->stream));
+  HIPCHK(launch::permute(op->part.n, 1, dst, op->part.n, from, op->part.n, op->bufs.d_perm,
+                         op->stream));
 }
 // `cols` device columns (internal order, ld = n) out to the caller, in the caller's order.
 void download_vec(tpl_op_s* op, double* dst, const double* src, int64_t cols, int mem) {
-  if (cols == 0 || op->n == 0) return;
+  const int64_t n = op->part.n;
+  if (cols == 0 || n == 0) return;
   // one vector, or columns of the basis: nothing else is ever this wide
   if (cols < 0 || (cols > 1 && (src != op->d_V || (size_t)cols > op->vcols)))
     fail(TPL_ERR_INVALID_ARGUMENT, "download_vec: column count exceeds its source");
-  if (!op->d_perm) {
-    HIPCHK(hipMemcpyAsync(dst, src, cols * op->n * sizeof(double),
+  if (!op->bufs.d_perm) {
+    HIPCHK(hipMemcpyAsync(dst, src, cols * n * sizeof(double),
                           mem == TPL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                           op->stream));
     return;
   }
   if (mem == TPL_MEM_DEVICE) {
-    HIPCHK(launch::permute(op->n, (int)cols, dst, op->n, src, op->n, op->d_iperm, op->stream));
+    HIPCHK(launch::permute(n, (int)cols, dst, n, src, n, op->bufs.d_iperm, op->stream));
     return;
   }
   for (int64_t c = 0; c < cols; ++c) {  // through the staging vector, a column at a time
-    HIPCHK(launch::permute(op->n, 1, op->d_stage, op->n, src + c * op->n, op->n, op->d_iperm,
+    HIPCHK(launch::permute(n, 1, op->bufs.d_stage, n, src + c * n, n, op->bufs.d_iperm,
                            op->stream));
-    HIPCHK(hipMemcpyAsync(dst + c * op->n, op->d_stage, op->n * sizeof(double),
+    HIPCHK(hipMemcpyAsync(dst + c * n, op->bufs.d_stage, n * sizeof(double),
                           hipMemcpyDeviceToHost, op->stream));
   }
 }
@@ -604,14 +610,14 @@ void dist_allgather(tpl_op_s* op, double* base, size_t count) {
 // the rows other ranks reference into this rank's halo slot (halo_pack, k_permute — issued
 // before the collective group) and all-gather the slots only (hH doubles each).
 void halo_pack(tpl_op_s* op, double* G) {
-  if (!op->halo || op->halo_send.empty()) return;
-  HIPCHK(launch::permute((int64_t)op->halo_send.size(), 1,
-                         G + op->ld + (size_t)op->dist->rank * op->hH, 0, G, 0,
+  if (!op->part.halo || op->part.halo_send.empty()) return;
+  HIPCHK(launch::permute((int64_t)op->part.halo_send.size(), 1,
+                         G + op->ld + (size_t)op->dist->rank * op->part.hH, 0, G, 0,
                          op->d_halo_send, op->stream));
 }
 void gather_vec(tpl_op_s* op, double* G) {
-  if (!op->halo) dist_allgather(op, G, (size_t)op->ld);
-  else if (op->hH > 0) dist_allgather(op, G + op->ld, (size_t)op->hH);
+  if (!op->part.halo) dist_allgather(op, G, (size_t)op->ld);
+  else if (op->part.hH > 0) dist_allgather(op, G + op->ld, (size_t)op->part.hH);
 }
 void dist_group(tpl_op_s* op, bool begin) {
   if (op->dist && op->dist->comm) NCCLCHK(begin ? ncclGroupStart() : ncclGroupEnd());
@@ -645,12 +651,12 @@ void enqueue_reorth(tpl_op_s* op, int j, int mode) {
   double* r = op->R[(j + 1) % 3];
   for (int pass = 0; pass < 2; ++pass) {
     const int* sk = (mode == 2 && pass == 1) ? skip : nullptr;
-    HIPCHK(launch::reorth_dot(op->n, cols, op->d_V, r, P, G2, E, sk, op->stream));
+    HIPCHK(launch::reorth_dot(op->part.n, cols, op->d_V, r, P, G2, E, sk, op->stream));
     HIPCHK(launch::reorth_reduce(cols, P, G2, h, sk, op->stream));
     // the last update rewrites the ||r||^2 partials that k_p1_spmv(j+1) reduces; in the
     // selective mode the first one writes its own partials for the decision
     double* pn = pass == 1 ? op->S.Pb : (mode == 2 ? Pb1 : nullptr);
-    HIPCHK(launch::reorth_update(op->n, cols, op->d_V, r, h, pn, G2, E, sk, op->stream));
+    HIPCHK(launch::reorth_update(op->part.n, cols, op->d_V, r, h, pn, G2, E, sk, op->stream));
     if (mode == 2 && pass == 0)
       HIPCHK(launch::reorth_decide(op->S, Pb1, G2, skip, rec, op->stream));
   }
@@ -661,7 +667,7 @@ void enqueue_reorth(tpl_op_s* op, int j, int mode) {
 void enqueue_p1_prologue(tpl_op_s* op) {
   const CsrDev A = csr_dev(op);
   HIPCHK(launch::p1_init(A, op->S, op->b, op->stream));
-  if (op->hybrid) {  // every column this rank gathers is local: only the norm partials move
+  if (op->part.hybrid) {  // every column this rank gathers is local: only the norm partials move
     if (op->pb_ld > 0) {
       dist_allgather(op, op->d_pball, (size_t)op->pb_ld);
     } else {
@@ -683,7 +689,7 @@ void enqueue_p1_prologue(tpl_op_s* op) {
 // (the alpha total; with replicated long rows their partials travel with it), (b) after
 // the AXPY (the beta total; with row blocks r_{j+1} travels with it).
 void enqueue_p1_exchange_a(tpl_op_s* op, const CsrDev& A) {
-  if (op->hybrid) {
+  if (op->part.hybrid) {
     // ONE all-gather: each rank's long-row partials and its short-chunk alpha partials
     // travel in one segment (one collective's latency per SpMV); every rank then finishes
     // the long rows itself (replicated), reduces each rank's alpha partials to its total
@@ -696,7 +702,7 @@ void enqueue_p1_exchange_a(tpl_op_s* op, const CsrDev& A) {
   }
 }
 void enqueue_p1_exchange_b(tpl_op_s* op, const CsrDev& A, int j) {
-  if (op->hybrid) {
+  if (op->part.hybrid) {
     if (op->pb_ld > 0) {
       // round 6: every rank's norm partials travel (pb_ld doubles per rank) and the next
       // k_p1_spmv reduces each rank's itself — no rank-total launch between k_p1_axpy and
@@ -720,7 +726,7 @@ void enqueue_p1_exchange_b(tpl_op_s* op, const CsrDev& A, int j) {
 }
 // The exchange after pass-two step j's SpMV launch.
 void enqueue_p2_exchange(tpl_op_s* op, int j) {
-  if (op->hybrid) {
+  if (op->part.hybrid) {
     const size_t nl = op->lay.lrows.size();
     if (nl) dist_allgather(op, op->d_yall, nl + 1);
   } else {
@@ -738,7 +744,7 @@ void enqueue_p1_step(tpl_op_s* op, int j, int k, double* Vcol, bool elim = false
   HIPCHK(launch::p1_spmv(A, op->S, rG_of(op, j), r_of(op, j), j >= 2 ? r_of(op, j - 1) : nullptr,
                          op->W, Vcol, j, op->stream, st1));
   if (op->dist) enqueue_p1_exchange_a(op, A);
-  if (op->hybrid)
+  if (op->part.hybrid)
     HIPCHK(launch::long_epi_p1(A, op->S, op->d_yall, op->dist->nranks, r_of(op, j),
                                j >= 2 ? r_of(op, j - 1) : nullptr, op->W, Vcol,
                                op->d_rsum + op->dist->nranks, j, op->stream));
@@ -758,7 +764,7 @@ void enqueue_pass1(tpl_op_s* op, size_t k, bool storeV, int reorth, bool elim = 
   enqueue_p1_prologue(op);
   const int js = stamped ? stamp_first(k) : 0;
   for (int j = 1; j <= (int)k; ++j) {
-    double* Vcol = storeV ? op->d_V + (size_t)(j - 1) * op->n : nullptr;
+    double* Vcol = storeV ? op->d_V + (size_t)(j - 1) * op->part.n : nullptr;
     const int i = j - js;  // stamp slots: spmv of step js + i at 2i, its axpy at 2i + 1
     unsigned long long* st1 = js && i >= 0 && i <= kStampSteps ? op->d_stamps + 2 * i : nullptr;
     unsigned long long* st2 = js && i >= 0 && i < kStampSteps ? op->d_stamps + 2 * i + 1 : nullptr;
@@ -768,9 +774,9 @@ void enqueue_pass1(tpl_op_s* op, size_t k, bool storeV, int reorth, bool elim = 
 }
 
 void enqueue_pass2_init(tpl_op_s* op, size_t steps, double* Vout) {
-  HIPCHK(launch::p2_init(op->n, op->S, op->b, op->V2[1], op->x, Vout, 0, op->stream));
+  HIPCHK(launch::p2_init(op->part.n, op->S, op->b, op->V2[1], op->x, Vout, 0, op->stream));
   HIPCHK(launch::p2_coefs(op->S, (int)steps, 0, op->stream));
-  if (op->dist && !op->hybrid) {
+  if (op->dist && !op->part.hybrid) {
     halo_pack(op, op->V2G[1]);
     gather_vec(op, op->V2G[1]);
   }
@@ -778,12 +784,12 @@ void enqueue_pass2_init(tpl_op_s* op, size_t steps, double* Vout) {
 void enqueue_pass2_steps(tpl_op_s* op, size_t steps, double* Vout) {
   const CsrDev A = csr_dev(op);
   for (int j = 1; j < (int)steps; ++j) {
-    double* Vcol = Vout ? Vout + (size_t)j * op->n : nullptr;
+    double* Vcol = Vout ? Vout + (size_t)j * op->part.n : nullptr;
     const int nflush = p2_flush(j, (int)steps - 1);
     HIPCHK(launch::p2_spmv(A, op->S, op->V2G[j % 3], op->V2[j % 3],
                            j >= 2 ? op->V2[(j - 1) % 3] : nullptr, op->V2[(j + 1) % 3], op->x,
                            Vcol, j, nflush, op->stream));
-    if (op->hybrid) {
+    if (op->part.hybrid) {
       enqueue_p2_exchange(op, j);
       HIPCHK(launch::long_epi_p2(A, op->S, op->d_yall, op->dist->nranks, op->V2[j % 3],
                                  j >= 2 ? op->V2[(j - 1) % 3] : nullptr, op->V2[(j + 1) % 3],
@@ -813,7 +819,7 @@ void enqueue_ftk_only(tpl_op_s* op, size_t k, int f, int scale) {
 }
 void enqueue_ftk_dev(tpl_op_s* op, size_t k, int f) {
   enqueue_ftk_only(op, k, f, 1);
-  HIPCHK(launch::p2_init(op->n, op->S, op->b, op->V2[1], op->x, nullptr, 1, op->stream));
+  HIPCHK(launch::p2_init(op->part.n, op->S, op->b, op->V2[1], op->x, nullptr, 1, op->stream));
   HIPCHK(launch::p2_coefs(op->S, (int)k, 1, op->stream));
 }
 void enqueue_pass2_dyn_steps(tpl_op_s* op, size_t k) {
@@ -824,7 +830,7 @@ void enqueue_pass2_dyn_steps(tpl_op_s* op, size_t k) {
                            nullptr, j, j % 3 == 0 ? 3 : 0, op->stream));
 }
 void enqueue_pass2_tail(tpl_op_s* op) {
-  HIPCHK(launch::p2_tail(op->n, op->S, op->x, op->V2, op->stream));
+  HIPCHK(launch::p2_tail(op->part.n, op->S, op->x, op->V2, op->stream));
 }
 
 template <class Enq>
@@ -979,45 +985,47 @@ void call_ftk(tpl_ftk_fn f, void* user, const HostDecomp& d, std::vector<double>
 }
 
 void zero_out(tpl_op_s* op, double* x_out, int mem) {
-  if (op->n == 0) return;
+  if (op->part.n == 0) return;
   if (mem == TPL_MEM_DEVICE) {
-    HIPCHK(hipMemsetAsync(x_out, 0, op->n * sizeof(double), op->stream));
+    HIPCHK(hipMemsetAsync(x_out, 0, op->part.n * sizeof(double), op->stream));
     sync_checked(op);
   } else {
-    std::memset(x_out, 0, op->n * sizeof(double));
+    std::memset(x_out, 0, op->part.n * sizeof(double));
   }
 }
 
-// Layout, vectors and events of a freshly filled operator (single GPU or one rank
-// of a partition; the vector stride ld is common to all ranks).
 // Vector stride ld, common to all ranks (the gathered vector holds rank r's block at r * ld).
 void set_stride(tpl_op_s* op) {
-  if (op->halo) {  // [own block | nranks x hH halo slots]; fill_halo sized and checked it
-    op->ld = ((std::max<int64_t>(op->n, 1) + 63) / 64) * 64;
+  const RankPlan& part = op->part;
+  if (part.halo) {  // [own block | nranks x hH halo slots]; the row split sized and checked it
+    op->ld = padded_stride(part.n);
     return;
   }
-  const int R = op->dist && !op->hybrid ? op->dist->nranks : 1;  // gathered vector copies
-  int64_t widest = op->n;
-  if (op->dist && !op->hybrid)
-    for (int r = 0; r < R; ++r) widest = std::max(widest, op->starts[r + 1] - op->starts[r]);
-  op->ld = ((std::max<int64_t>(widest, 1) + 63) / 64) * 64;
+  const int R = op->dist && !part.hybrid ? op->dist->nranks : 1;  // gathered vector copies
+  int64_t widest = part.n;
+  if (op->dist && !part.hybrid)
+    for (int r = 0; r < R; ++r) widest = std::max(widest, part.starts[r + 1] - part.starts[r]);
+  op->ld = padded_stride(widest);
   // gathered column indices (ColMap: r * ld + local) are int32 on the device
   if ((int64_t)R * op->ld >= (int64_t)INT32_MAX)
     fail(TPL_ERR_UNSUPPORTED, "row blocks too unbalanced: nranks x widest block >= 2^31");
 }
 
+// Layout, vectors and events of a freshly planned operator (single GPU or one rank
+// of a partition; the vector stride ld is common to all ranks).
 void init_op(tpl_op_s* op) {
-  const int R = op->dist && !op->hybrid ? op->dist->nranks : 1;  // gathered vector copies
+  const int R = op->dist && !op->part.hybrid ? op->dist->nranks : 1;  // gathered vector copies
   set_stride(op);
-  rebuild_schedule(op);
+  rebuild_schedule(op, op->sp, op->reorder);
   // gathered: b, R0..2, V2_0..2, tmp (R x ld each; halo: ld + R x hH); local: W, x (ld each)
-  const size_t gl = op->halo ? (size_t)op->ld + (size_t)R * op->hH : (size_t)R * op->ld;
+  const size_t gl = op->part.halo ? (size_t)op->ld + (size_t)R * op->part.hH : (size_t)R * op->ld;
   const size_t gathered = 8 * gl, local = 2 * (size_t)op->ld;
   dev_alloc(op, &op->d_vecs, (gathered + local) * sizeof(double));
   HIPCHK(hipMemset(op->d_vecs, 0, (gathered + local) * sizeof(double)));
   double* p = op->d_vecs;
-  const size_t own = (size_t)(op->dist && !op->hybrid && !op->halo ? op->dist->rank : 0) * op->ld;
-  upload(op, &op->d_halo_send, op->halo_send);
+  const bool blocks = op->dist && !op->part.hybrid && !op->part.halo;  // whole blocks gathered
+  const size_t own = (size_t)(blocks ? op->dist->rank : 0) * op->ld;
+  upload(op, &op->d_halo_send, op->part.halo_send);
   op->bG = p;
   p += gl;
   for (int i = 0; i < 3; ++i, p += gl) op->RG[i] = p;
@@ -1034,18 +1042,18 @@ void init_op(tpl_op_s* op) {
   if (op->dist) {
     // [nranks alpha totals | long-row alpha partials (hybrid) | nranks norm totals]
     const size_t nr = (size_t)op->dist->nranks;
-    const size_t cnt = 2 * nr + (op->hybrid ? (size_t)long_epi_blocks(op) : 0);
+    const size_t cnt = 2 * nr + (op->part.hybrid ? (size_t)long_epi_blocks(op) : 0);
     dev_alloc(op, &op->d_rsum, cnt * sizeof(double));
     HIPCHK(hipMemset(op->d_rsum, 0, cnt * sizeof(double)));
-    if (op->hybrid) {
+    if (op->part.hybrid) {
       // every rank's chunk count (each rank's short rows are a contiguous block of the
       // global split, chunked by kChunkRows: every rank computes all counts alike)
-      if ((int)op->nch.size() != op->dist->nranks ||
-          op->nch[op->dist->rank] != (int32_t)op->lay.c_base.size())
+      if ((int)op->part.nch.size() != op->dist->nranks ||
+          op->part.nch[op->dist->rank] != (int32_t)op->lay.c_base.size())
         fail(TPL_ERR_UNSUPPORTED, "replicated partition: chunk counts disagree with the layout");
-      const int32_t nmax = *std::max_element(op->nch.begin(), op->nch.end());
+      const int32_t nmax = *std::max_element(op->part.nch.begin(), op->part.nch.end());
       op->y_ld1 = (int32_t)op->lay.lrows.size() + nmax;
-      upload(op, &op->d_nch, op->nch);
+      upload(op, &op->d_nch, op->part.nch);
       // pass one strides the all-gather by y_ld1, pass two and tpl_op_apply by n_long + 1
       const size_t ya = nr * (size_t)std::max<int64_t>(op->y_ld1, (int64_t)op->lay.lrows.size() + 1);
       dev_alloc(op, &op->d_yall, ya * sizeof(double));
@@ -1054,10 +1062,10 @@ void init_op(tpl_op_s* op) {
       // counts from the global split) and k_p1_spmv reduces each rank's with the tree the
       // rank-total launch applied — one launch less per pass-one step, the same bits —
       // while they fit one load per lane and rank (≤ kPbRanks ranks, ≤ kTPB partials)
-      if ((int)op->g2s.size() != op->dist->nranks ||
-          op->g2s[op->dist->rank] != op->lay.G2)
+      if ((int)op->part.g2s.size() != op->dist->nranks ||
+          op->part.g2s[op->dist->rank] != op->lay.G2)
         fail(TPL_ERR_UNSUPPORTED, "replicated partition: block counts disagree with the layout");
-      const int32_t g2max = *std::max_element(op->g2s.begin(), op->g2s.end());
+      const int32_t g2max = *std::max_element(op->part.g2s.begin(), op->part.g2s.end());
       if (op->dist->nranks <= kPbRanks && g2max <= kTPB) {
         op->pb_ld = g2max;
         dev_alloc(op, &op->d_pball, nr * (size_t)g2max * sizeof(double));
@@ -1070,248 +1078,33 @@ void init_op(tpl_op_s* op) {
   for (hipEvent_t& e : op->tev) HIPCHK(hipEventCreate(&e));
 }
 
-// Contiguous blocks over items 0..m-1 with cost prefix[m+1]: cut where the prefix
-// crosses r/nranks of the total; every block keeps at least one item.
-void balanced_cuts(const std::vector<double>& prefix, int nranks, int64_t* starts) {
-  const int64_t m = (int64_t)prefix.size() - 1;
-  const double total = prefix[m];
-  starts[0] = 0;
-  int64_t i = 0;
-  for (int r = 1; r < nranks; ++r) {
-    const double target = total * r / nranks;
-    while (i < m && prefix[i] < target) ++i;
-    starts[r] = std::min<int64_t>(std::max<int64_t>(i, starts[r - 1] + 1), m - (nranks - r));
-    i = starts[r];
+// The one way to make an operator: `part` on ctx's device and stream, as a rank of `dist`
+// (or nullptr: single GPU), ready for init_op. ctx == nullptr: a host-only plan
+// (tpl_plan_create), which gets a stride and a layout and nothing on a device.
+std::unique_ptr<tpl_op_s> make_op(tpl_ctx_s* ctx, tpl_dist_s* dist, RankPlan&& part) {
+  auto op = std::make_unique<tpl_op_s>();
+  op->part = std::move(part);
+  op->sp.long_from = op->part.long_from;
+  op->sp.elem_rows = op->part.elem_rows;
+  op->dist = dist;
+  op->plan_only = !ctx;
+  if (ctx) {
+    op->device = ctx->device;
+    op->stream = ctx->stream;
+    op->eager = dist && dist->comm == nullptr;
   }
-  starts[nranks] = m;
+  return op;
 }
 
-// Host half of tpl_dist_op_create_replicated (and of its tpl_plan_create): the short-row
-// split, this rank's rows in their order and its local CSR. op->n .. op->nch.
-void fill_replicated(tpl_op_s* op, int R, int me, int64_t n, const int64_t* row_ptr,
-                     const int32_t* col_idx, const double* vals) {
-  const int64_t nnz = row_ptr[n];
-  if (n < 1 || n >= INT32_MAX / 2 || nnz >= INT32_MAX || row_ptr[0] != 0)
-    fail(TPL_ERR_INVALID_ARGUMENT, "bad CSR sizes");
-  if (nnz > 0 && !vals) fail(TPL_ERR_INVALID_ARGUMENT, "col_idx/vals is NULL");
-  check_csr(n, n, row_ptr, col_idx);
-  std::vector<int32_t> rp32(n + 1);
-  for (int64_t i = 0; i <= n; ++i) rp32[i] = (int32_t)row_ptr[i];
-  // short / long rows by the global rule; long rows are replicated on every rank
-  const int32_t T = short_row_threshold(n, rp32, -1);
-  std::vector<int64_t> S, Lr;
-  std::vector<int32_t> lidx(n, -1);
-  for (int64_t i = 0; i < n; ++i) {
-    if (rp32[i + 1] - rp32[i] > T) {
-      lidx[i] = (int32_t)Lr.size();
-      Lr.push_back(i);
-    } else {
-      S.push_back(i);
-    }
-  }
-  if ((int64_t)S.size() < R) fail(TPL_ERR_UNSUPPORTED, "fewer short rows than ranks");
-  // short rows in contiguous blocks balanced by bytes: the row itself plus the
-  // long-row entries in its column, which the owner of that column computes
-  std::vector<int32_t> longcnt(n, 0);
-  for (int64_t l : Lr)
-    for (int64_t q = row_ptr[l]; q < row_ptr[l + 1]; ++q) longcnt[col_idx[q]]++;
-  std::vector<double> prefix(S.size() + 1, 0.0);
-  for (size_t p = 0; p < S.size(); ++p) {
-    const int64_t i = S[p];
-    prefix[p + 1] = prefix[p] + 12.0 * (double)(rp32[i + 1] - rp32[i] + longcnt[i]) + 40.0;
-  }
-  std::vector<int64_t> cut(R + 1);
-  balanced_cuts(prefix, R, cut.data());
-  std::vector<int32_t> owner(n, -1);
-  for (int r = 0; r < R; ++r)
-    for (int64_t p = cut[r]; p < cut[r + 1]; ++p) owner[S[p]] = r;
-  // halo-free check (all ranks decide alike: they all see the whole matrix)
-  for (int64_t i : S)
-    for (int64_t q = row_ptr[i]; q < row_ptr[i + 1]; ++q) {
-      const int32_t c = col_idx[q];
-      if (lidx[c] < 0 && owner[c] != owner[i])
-        fail(TPL_ERR_UNSUPPORTED, "a short row references a short row of another rank "
-                                  "(use the row-partitioned operator)");
-    }
-  op->hybrid = true;
-  op->n_glob = n;
-  const int64_t ns = cut[me + 1] - cut[me], nl = (int64_t)Lr.size();
-  op->ns_local = ns;
-  op->n = ns + nl;
-  // this rank's short rows; in the locality order (tpl_layout.h locality_order, the
-  // same key over the replicated long rows' ranks) when the rank's rows fit the auto
-  // rule. The local order is the caller's to follow through tpl_op_local_rows, so no
-  // vector is permuted on the device.
-  std::vector<int64_t> mine(S.begin() + cut[me], S.begin() + cut[me + 1]);
-  if (nl > 0 && op->n <= kReorderAutoMaxRows) {
-    // lidx is each long row's rank among the long rows, as locality_order ranks them
-    locality_sort(mine, row_ptr, col_idx, lidx.data(), (int32_t)nl, op->sp.order_groups);
-    op->local_order = true;
-  }
-  op->g2l.assign(n, -1);
-  op->local_rows.resize(op->n);
-  for (int64_t p = 0; p < ns; ++p) {
-    op->g2l[mine[p]] = (int32_t)p;
-    op->local_rows[p] = mine[p];
-  }
-  for (int64_t l = 0; l < nl; ++l) {
-    op->g2l[Lr[l]] = (int32_t)(ns + l);
-    op->local_rows[ns + l] = Lr[l];
-  }
-  // local CSR in local column indices, each row ascending: own short rows whole; long
-  // rows restricted to the columns this rank owns (long-row columns: rank 0). The
-  // long rows' 8 column slices then split this rank's own columns, so every XCD
-  // gets a share of the long-row work.
-  op->h_rowptr.assign(1, 0);
-  std::vector<std::pair<int32_t, double>> row;
-  for (int64_t p = 0; p < op->n; ++p) {
-    const int64_t i = op->local_rows[p];
-    const bool is_long = p >= ns;
-    row.clear();
-    for (int64_t q = row_ptr[i]; q < row_ptr[i + 1]; ++q) {
-      const int32_t c = col_idx[q];
-      if (is_long && !(lidx[c] < 0 ? owner[c] == me : me == 0)) continue;
-      row.emplace_back(op->g2l[c], vals[q]);
-    }
-    std::sort(row.begin(), row.end(),
-              [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& b) {
-                return a.first < b.first;
-              });
-    for (const auto& e : row) {
-      op->h_col.push_back(e.first);
-      op->h_val.push_back(e.second);
-    }
-    op->h_rowptr.push_back((int32_t)op->h_col.size());
-  }
-  op->nnz = (int64_t)op->h_col.size();
-  op->sp.long_from = ns;
-  op->nch.resize(R);
-  op->g2s.resize(R);
-  for (int r = 0; r < R; ++r) {
-    op->nch[r] = (int32_t)((cut[r + 1] - cut[r] + kChunkRows - 1) / kChunkRows);
-    int64_t E = 0;
-    elem_geometry(cut[r + 1] - cut[r] + nl, op->sp, op->g2s[r], E);
-  }
-  // Up to kPbRanks ranks: element-wise blocks wide enough that no rank holds more than kTPB
-  // norm partials, so pass one's SpMV reduces every rank's gathered partials itself (one
-  // load per lane and rank) and no rank-total launch remains — when that needs at most
-  // 2 kElemRows rows per block. Measured on the 5M-arc instance (round 6, rank shares
-  // through one RCCL rank, profiles/r06_rank_share_5m_wide.txt): N = 8, 306 -> 246
-  // partials at 2,560 rows per block, slowest share 14.35 -> 13.78 ms; N = 4, 5,120 rows
-  // per block, 20.69 -> 21.29 ms (k_p1_axpy's wider blocks cost more than the launch), so
-  // not applied there. Every rank applies the same rule to the same split, so all agree
-  // on every rank's count.
-  int64_t rows_max = 0;
-  for (int r = 0; r < R; ++r) rows_max = std::max<int64_t>(rows_max, cut[r + 1] - cut[r] + nl);
-  const int64_t er_gp = (((rows_max + kTPB - 1) / kTPB) + 511) / 512 * 512;
-  if (R <= kPbRanks && op->sp.elem_rows <= 0 && er_gp <= 2 * kElemRows &&
-      *std::max_element(op->g2s.begin(), op->g2s.end()) > kTPB) {
-    op->sp.elem_rows = (int)er_gp;
-    for (int r = 0; r < R; ++r) {
-      int64_t E = 0;
-      elem_geometry(cut[r + 1] - cut[r] + nl, op->sp, op->g2s[r], E);
-    }
-  }
-}
-
-// Host half of a row-block rank from the WHOLE matrix (TPL_PLAN_ROWS, TPL_PLAN_HALO,
-// tpl_dist_op_create_halo): block `me` of `starts` (nullptr: the tpl_dist_partition
-// split), its rows with global column indices. halo: also the halo plan — B_q = the rows
-// of rank q's block that a row of another rank references (one pass over the nonzeros),
-// hH = max_q |B_q|, this rank's send list (B_me in local indices) and the column table:
-// own column c -> c - starts[me], remote column c in B_q -> ld + q hH + (c's rank in B_q).
-// The layout is built from the same CSR and global-column slices as plain row blocks, so
-// the two hold the same reduction order; only the gathered positions differ.
-void fill_rows(tpl_op_s* op, int R, int me, int64_t n, const int64_t* starts,
-               const int64_t* row_ptr, const int32_t* col_idx, const double* vals, bool halo) {
-  if (n < R) fail(TPL_ERR_INVALID_ARGUMENT, "fewer rows than ranks");
-  if (n >= INT32_MAX / 2) fail(TPL_ERR_UNSUPPORTED, "n must be < 2^30");
-  if (row_ptr[0] != 0) fail(TPL_ERR_INVALID_ARGUMENT, "row_ptr must start at 0");
-  if (row_ptr[n] > 0 && (!vals || !col_idx)) fail(TPL_ERR_INVALID_ARGUMENT, "col_idx/vals is NULL");
-  check_csr(n, n, row_ptr, col_idx);
-  op->starts.resize(R + 1);
-  if (starts) {
-    if (starts[0] != 0 || starts[R] != n) fail(TPL_ERR_INVALID_ARGUMENT, "bad partition");
-    for (int r = 0; r < R; ++r)
-      if (starts[r + 1] <= starts[r]) fail(TPL_ERR_INVALID_ARGUMENT, "empty or unordered block");
-    op->starts.assign(starts, starts + R + 1);
-  } else {
-    std::vector<double> prefix(n + 1);
-    for (int64_t i = 0; i <= n; ++i) prefix[i] = 12.0 * (double)row_ptr[i] + 40.0 * (double)i;
-    balanced_cuts(prefix, R, op->starts.data());
-  }
-  const int64_t r0 = op->starts[me], r1 = op->starts[me + 1];
-  op->n = r1 - r0;
-  op->n_glob = n;
-  op->nnz = row_ptr[r1] - row_ptr[r0];
-  if (op->nnz >= INT32_MAX) fail(TPL_ERR_UNSUPPORTED, "nnz must be < 2^31");
-  op->h_rowptr.resize(op->n + 1);
-  for (int64_t i = 0; i <= op->n; ++i) op->h_rowptr[i] = (int32_t)(row_ptr[r0 + i] - row_ptr[r0]);
-  op->h_col.assign(col_idx + row_ptr[r0], col_idx + row_ptr[r1]);
-  op->h_val.assign(vals + row_ptr[r0], vals + row_ptr[r1]);
-  if (!halo) return;
-  const std::vector<int64_t>& st = op->starts;
-  std::vector<uint8_t> need(n, 0);
-  for (int r = 0; r < R; ++r)
-    for (int64_t q = row_ptr[st[r]]; q < row_ptr[st[r + 1]]; ++q) {
-      const int32_t c = col_idx[q];
-      if (c < st[r] || c >= st[r + 1]) need[c] = 1;
-    }
-  std::vector<int32_t> pos(n, -1);
-  int64_t H = 0;
-  for (int q = 0; q < R; ++q) {
-    int32_t m = 0;
-    for (int64_t c = st[q]; c < st[q + 1]; ++c)
-      if (need[c]) pos[c] = m++;
-    H = std::max<int64_t>(H, m);
-  }
-  op->halo = true;
-  op->hH = H;
-  const int64_t ld = ((std::max<int64_t>(op->n, 1) + 63) / 64) * 64;  // set_stride's
-  if (ld + (int64_t)R * H >= (int64_t)INT32_MAX)
-    fail(TPL_ERR_UNSUPPORTED, "halo partition: own block + nranks x halo width >= 2^31");
-  op->halo_send.clear();
-  for (int64_t c = r0; c < r1; ++c)
-    if (need[c]) op->halo_send.push_back((int32_t)(c - r0));
-  op->halo_map.assign(n, -1);
-  for (int64_t c = r0; c < r1; ++c) op->halo_map[c] = (int32_t)(c - r0);
-  for (int q = 0; q < R; ++q)
-    if (q != me)
-      for (int64_t c = st[q]; c < st[q + 1]; ++c)
-        if (pos[c] >= 0) op->halo_map[c] = (int32_t)(ld + (int64_t)q * H + pos[c]);
-}
-
-// The partition every binding's "auto" takes (tpl_dist_choose_partition): replicated long
-// rows when the matrix allows them, else halo row blocks when the halo is at most half the
-// widest block, else plain row blocks. Host only; the same answer on every rank.
-int choose_partition(int64_t n, const int64_t* row_ptr, const int32_t* col_idx, int R) {
-  if (!row_ptr || R < 1) fail(TPL_ERR_INVALID_ARGUMENT, "bad argument");
-  {
-    tpl_op_s tmp;
-    tpl_dist_s pd;
-    pd.nranks = R;
-    tmp.dist = &pd;
-    // the split's feasibility does not depend on the rank; the values are not read for it
-    std::vector<double> ones(std::max<int64_t>(row_ptr[n], 1), 1.0);
-    try {
-      fill_replicated(&tmp, R, 0, n, row_ptr, col_idx, ones.data());
-      tmp.dist = nullptr;
-      return TPL_PLAN_REPLICATED;
-    } catch (const Error& e) {
-      tmp.dist = nullptr;
-      if (e.code != TPL_ERR_UNSUPPORTED) throw;
-    }
-  }
-  tpl_op_s tmp;
-  tpl_dist_s pd;
-  pd.nranks = R;
-  tmp.dist = &pd;
-  std::vector<double> ones(std::max<int64_t>(row_ptr[n], 1), 1.0);
-  fill_rows(&tmp, R, 0, n, nullptr, row_ptr, col_idx, ones.data(), true);
-  tmp.dist = nullptr;
-  int64_t widest = 0;
-  for (int r = 0; r < R; ++r) widest = std::max<int64_t>(widest, tmp.starts[r + 1] - tmp.starts[r]);
-  return 2 * tmp.hH <= widest ? TPL_PLAN_HALO : TPL_PLAN_ROWS;
+// Where a k-step solve evaluates f(T_k): on the device for the built-in inv / exp of an
+// operator that is not partitioned, up to the mode's k (tpl_op_set_device_ftk).
+DevF device_f(const tpl_op_s* op, tpl_ftk_fn f, size_t k) {
+  const bool is_inv = f == &tpl_ftk_inv, is_exp = f == &tpl_ftk_exp;
+  const size_t kmax = !op->device_ftk ? 0
+                      : is_inv ? (op->device_ftk == 1 ? kDevFtkMaxK : kDevFtkAutoK)
+                      : is_exp ? kDevExpMaxK : 0;
+  if ((!is_inv && !is_exp) || op->dist || k > kmax) return kDevHost;
+  return is_exp ? kDevExp : kDevInv;
 }
 
 } // namespace
@@ -1364,24 +1157,9 @@ tpl_status tpl_op_create_csr(tpl_ctx_t ctx, int64_t n, int64_t nnz, const int64_
   return guarded([&] {
     if (!ctx || !out) fail(TPL_ERR_INVALID_ARGUMENT, "ctx/out is NULL");
     if (n < 0 || nnz < 0) fail(TPL_ERR_INVALID_ARGUMENT, "negative size");
-    if (n >= INT32_MAX || nnz >= INT32_MAX)
-      fail(TPL_ERR_UNSUPPORTED, "n and nnz must be < 2^31 (int32 device offsets)");
-    if (!row_ptr) fail(TPL_ERR_INVALID_ARGUMENT, "row_ptr is NULL");
-    if (nnz > 0 && !vals) fail(TPL_ERR_INVALID_ARGUMENT, "col_idx/vals is NULL");
-    if (row_ptr[n] != nnz) fail(TPL_ERR_INVALID_ARGUMENT, "row_ptr must start at 0 and end at nnz");
-    check_csr(n, n, row_ptr, col_idx);
+    RankPlan part = single_plan(n, nnz, row_ptr, col_idx, vals);
     HIPCHK(hipSetDevice(ctx->device));
-    auto op = std::make_unique<tpl_op_s>();
-    op->ctx = ctx;
-    op->device = ctx->device;
-    op->stream = ctx->stream;
-    op->n = n;
-    op->n_glob = n;
-    op->nnz = nnz;
-    op->h_rowptr.resize(n + 1);
-    for (int64_t i = 0; i <= n; ++i) op->h_rowptr[i] = (int32_t)row_ptr[i];
-    op->h_col.assign(col_idx, col_idx + nnz);
-    op->h_val.assign(vals, vals + nnz);
+    auto op = make_op(ctx, nullptr, std::move(part));
     init_op(op.get());
     *out = op.release();
   });
@@ -1407,12 +1185,12 @@ tpl_status tpl_op_destroy(tpl_op_t op) {
   });
 }
 
-int64_t tpl_op_nrows(tpl_op_t op) { return op ? op->n : -1; }
+int64_t tpl_op_nrows(tpl_op_t op) { return op ? op->part.n : -1; }
 int tpl_op_flags(tpl_op_t op) {
   if (!op) return -1;
   return (op->dist ? 1 : 0) | (op->eager ? 2 : 0) | (op->lay.val_i8 ? 4 : 0) |
          (op->lay.s_col16 ? 8 : 0) | (op->lay.b_col16 ? 16 : 0) | (op->last_one_graph ? 32 : 0) |
-         (!op->perm.empty() || op->local_order ? 64 : 0) | (op->pb_ld > 0 ? 128 : 0);
+         (!op->perm.empty() || op->part.local_order ? 64 : 0) | (op->pb_ld > 0 ? 128 : 0);
 }
 
 tpl_status tpl_op_set_reorder(tpl_op_t op, int mode) {
@@ -1421,16 +1199,15 @@ tpl_status tpl_op_set_reorder(tpl_op_t op, int mode) {
     if (mode < 0 || mode > 2) fail(TPL_ERR_INVALID_ARGUMENT, "reorder mode must be 0, 1 or 2");
     set_device(op);
     sync_checked(op);
-    op->reorder = mode;
-    rebuild_schedule(op);
+    rebuild_schedule(op, op->sp, mode);
   });
 }
 
 tpl_status tpl_op_permutation(tpl_op_t op, int32_t* perm) {
   return guarded([&] {
-    if (!op || (!perm && op->n > 0)) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!op || (!perm && op->part.n > 0)) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
     if (op->perm.empty())
-      for (int64_t i = 0; i < op->n; ++i) perm[i] = (int32_t)i;
+      for (int64_t i = 0; i < op->part.n; ++i) perm[i] = (int32_t)i;
     else
       std::copy(op->perm.begin(), op->perm.end(), perm);
   });
@@ -1440,27 +1217,28 @@ tpl_status tpl_op_set_value_format(tpl_op_t op, int compress) {
   return guarded([&] {
     if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
     set_device(op);
-    op->sp.compress_values = compress != 0;
-    op->sp.compress_cols = compress != 0;
+    SchedParams sp = op->sp;
+    sp.compress_values = compress != 0;
+    sp.compress_cols = compress != 0;
     sync_checked(op);
-    rebuild_schedule(op);
+    rebuild_schedule(op, sp, op->reorder);
   });
 }
-int64_t tpl_op_nnz(tpl_op_t op) { return op ? op->nnz : -1; }
+int64_t tpl_op_nnz(tpl_op_t op) { return op ? op->part.nnz : -1; }
 
 tpl_status tpl_op_apply(tpl_op_t op, const double* x, double* y, int mem) {
   return guarded([&] {
-    if (!op || ((!x || !y) && op->n > 0)) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!op || ((!x || !y) && op->part.n > 0)) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
     set_device(op);
-    if (op->n == 0) return;
+    if (op->part.n == 0) return;
     upload_vec(op, op->tmp, x, mem);
-    if (op->dist && !op->hybrid) {
+    if (op->dist && !op->part.hybrid) {
       halo_pack(op, op->tmpG);
       gather_vec(op, op->tmpG);
     }
     const CsrDev A = csr_dev(op);
     HIPCHK(launch::spmv(A, op->tmpG, op->W, op->stream));
-    if (op->hybrid && A.n_long > 0) {
+    if (op->part.hybrid && A.n_long > 0) {
       dist_allgather(op, op->d_yall, (size_t)A.y_ld);
       HIPCHK(launch::long_epi_y(A, op->d_yall, op->dist->nranks, op->W, op->stream));
     }
@@ -1517,11 +1295,11 @@ tpl_status tpl_lanczos_standard(tpl_op_t op, const double* b, int64_t b_len, siz
       // the callback's view in the caller's row order: each batch's new columns are
       // gathered into d_Vext (an n x k buffer, reordered operators only)
       double* Vview = op->d_V;
-      if (op->d_perm) {
+      if (op->bufs.d_perm) {
         if (op->vext_cols < k) {
           dev_free(op, op->d_Vext);
           op->vext_cols = 0;
-          dev_alloc(op, &op->d_Vext, (size_t)op->n * k * sizeof(double));
+          dev_alloc(op, &op->d_Vext, (size_t)op->part.n * k * sizeof(double));
           op->vext_cols = k;
         }
         Vview = op->d_Vext;
@@ -1533,13 +1311,14 @@ tpl_status tpl_lanczos_standard(tpl_op_t op, const double* b, int64_t b_len, siz
       for (int j0 = 1; j0 <= (int)k;) {
         const int j1 = std::min<int>((int)k, j0 + batch - 1);
         for (int j = j0; j <= j1; ++j) {
-          enqueue_p1_step(op, j, (int)k, op->d_V + (size_t)(j - 1) * op->n);
+          enqueue_p1_step(op, j, (int)k, op->d_V + (size_t)(j - 1) * op->part.n);
           if (reorth && j < (int)k) enqueue_reorth(op, j, reorth);
         }
         if (Vview != op->d_V)
-          HIPCHK(launch::permute(op->n, j1 - j0 + 1, Vview + (size_t)(j0 - 1) * op->n, op->n,
-                                 op->d_V + (size_t)(j0 - 1) * op->n, op->n, op->d_iperm,
-                                 op->stream));
+          HIPCHK(launch::permute(op->part.n, j1 - j0 + 1,
+                                 Vview + (size_t)(j0 - 1) * op->part.n, op->part.n,
+                                 op->d_V + (size_t)(j0 - 1) * op->part.n, op->part.n,
+                                 op->bufs.d_iperm, op->stream));
         d = fetch_decomp(op, k);
         bool go = true;
         for (int j = j0; j <= j1 && go; ++j) {
@@ -1548,7 +1327,7 @@ tpl_status tpl_lanczos_standard(tpl_op_t op, const double* b, int64_t b_len, siz
             go = false;
             break;
           }
-          go = cb((size_t)j, Vview, op->n, d.alphas, (size_t)j, d.betas, (size_t)j - 1,
+          go = cb((size_t)j, Vview, op->part.n, d.alphas, (size_t)j, d.betas, (size_t)j - 1,
                   cb_user) != 0;
           if (!go) stop_at = (size_t)j;
         }
@@ -1601,8 +1380,6 @@ tpl_status tpl_lanczos_pass_two(tpl_op_t op, const double* b, int64_t b_len, con
       fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
     ensure_state(op, steps);
     // decomposition -> device: norms[0], alphas, betas, y
-    std::vector<double> host(1 + 3 * op->kcap, 0.0);
-    (void)host;
     HIPCHK(hipMemcpyAsync(op->S.norms, &b_norm, sizeof(double), hipMemcpyHostToDevice, op->stream));
     HIPCHK(hipMemcpyAsync(op->S.alphas, alphas, steps * sizeof(double), hipMemcpyHostToDevice,
                           op->stream));
@@ -1632,17 +1409,14 @@ tpl_status tpl_lanczos_two_pass(tpl_op_t op, const double* b, int64_t b_len, siz
     check_k(k);
     // the built-in inv / exp on the device: the whole solve one graph (pass one, f(T_k)
     // from the device alpha / beta, pass two), no host round trip between the passes
-    const bool is_inv = f == &tpl_ftk_inv, is_exp = f == &tpl_ftk_exp;
-    const size_t kmax = !op->device_ftk ? 0
-                        : is_inv ? (op->device_ftk == 1 ? kDevFtkMaxK : kDevFtkAutoK)
-                        : is_exp ? kDevExpMaxK : 0;
+    const DevF dev_f = device_f(op, f, k);
     bool have_p1 = false;  // pass one already ran (the device handed f back to the host)
-    if ((is_inv || is_exp) && !op->dist && k <= kmax) {
+    if (dev_f != kDevHost) {
       // inv: the host solver's operations in its order, bit for bit (src/solvers.rs:148-174);
       // exp: a parallel evaluation of the same function (k_ftk_exp), EVD-class accuracy
       ensure_state(op, k);
       upload_vec(op, op->b, b, mem);
-      run_two_pass_dev(op, k, is_exp ? kDevExp : kDevInv);
+      run_two_pass_dev(op, k, dev_f);
       download_vec(op, x_out, op->x, 1, mem);
       HIPCHK(hipMemcpyAsync(op->h_state, op->d_state, kFlagBytes, hipMemcpyDeviceToHost,
                             op->stream));
@@ -1696,18 +1470,14 @@ tpl_status tpl_lanczos(tpl_op_t op, const double* b, int64_t b_len, size_t k, tp
     // the built-in inv / exp on the device after the standard pass, then the
     // reconstruction: no host round trip (the same rules as tpl_lanczos_two_pass; y'
     // unscaled, the GEMV multiplies by ||b||)
-    const bool is_inv = f == &tpl_ftk_inv, is_exp = f == &tpl_ftk_exp;
-    const size_t kmax = !op->device_ftk ? 0
-                        : is_inv ? (op->device_ftk == 1 ? kDevFtkMaxK : kDevFtkAutoK)
-                        : is_exp ? kDevExpMaxK : 0;
-    const bool dev_f = (is_inv || is_exp) && !op->dist && k <= kmax;
+    const DevF dev_f = device_f(op, f, k);
     // 1. standard pass, V_k in HBM (src/solvers.rs:61); a device inv's LU eliminated
     //    during it
-    run_pass_one(op, b, k, mem, true, false, dev_f && is_inv);
+    run_pass_one(op, b, k, mem, true, false, dev_f == kDevInv);
     op->last_one_graph = false;
-    if (dev_f) {
-      enqueue_ftk_only(op, k, is_exp ? kDevExp : kDevInv, 0);
-      HIPCHK(launch::gemv_recon(op->n, -1, op->S, op->d_V, op->x, op->stream));
+    if (dev_f != kDevHost) {
+      enqueue_ftk_only(op, k, dev_f, 0);
+      HIPCHK(launch::gemv_recon(op->part.n, -1, op->S, op->d_V, op->x, op->stream));
       const HostDecomp dd = fetch_decomp(op, k);
       if (dd.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
       if (dd.steps == 0) {
@@ -1734,7 +1504,7 @@ tpl_status tpl_lanczos(tpl_op_t op, const double* b, int64_t b_len, size_t k, tp
     HIPCHK(hipMemcpyAsync(op->S.y, y.data(), d.steps * sizeof(double), hipMemcpyHostToDevice,
                           op->stream));
     // 3. x = ||b|| V_k y' (:96-104)
-    HIPCHK(launch::gemv_recon(op->n, (int)d.steps, op->S, op->d_V, op->x, op->stream));
+    HIPCHK(launch::gemv_recon(op->part.n, (int)d.steps, op->S, op->d_V, op->x, op->stream));
     download_vec(op, x_out, op->x, 1, mem);
     sync_checked(op);
   });
@@ -1758,10 +1528,11 @@ tpl_status tpl_op_set_schedule(tpl_op_t op, int32_t short_row_max, int32_t max_g
   return guarded([&] {
     if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
     set_device(op);
-    if (short_row_max != 0) op->sp.short_row_max = short_row_max < 0 ? -1 : short_row_max;
-    if (max_g2 > 0) op->sp.max_g2 = max_g2;
+    SchedParams sp = op->sp;
+    if (short_row_max != 0) sp.short_row_max = short_row_max < 0 ? -1 : short_row_max;
+    if (max_g2 > 0) sp.max_g2 = max_g2;
     sync_checked(op);
-    rebuild_schedule(op);
+    rebuild_schedule(op, sp, op->reorder);
   });
 }
 
@@ -1779,9 +1550,10 @@ tpl_status tpl_op_set_slices(tpl_op_t op, int32_t slices) {
       fail(TPL_ERR_INVALID_ARGUMENT,
            "slices must be 0 (auto) or a power of two up to " + std::to_string(kSlices));
     set_device(op);
-    op->sp.slices = slices;
+    SchedParams sp = op->sp;
+    sp.slices = slices;
     sync_checked(op);
-    rebuild_schedule(op);
+    rebuild_schedule(op, sp, op->reorder);
   });
 }
 
@@ -1798,7 +1570,7 @@ double tpl_kernel_algo_bytes(tpl_op_t op, int kernel) {
   // nonzero, int32 row_ptr, x read once, y written once). The fused kernels add the
   // epilogue vectors they must touch (DESIGN.md "Algorithmic bytes").
   if (!op) return 0.0;
-  const double n = (double)op->n, nnz = (double)op->nnz;
+  const double n = (double)op->part.n, nnz = (double)op->part.nnz;
   const double spmv = 12.0 * nnz + 4.0 * (n + 1.0) + 16.0 * n;
   switch (kernel) {
     case TPL_KERNEL_SPMV: return spmv;
@@ -1811,13 +1583,13 @@ double tpl_kernel_algo_bytes(tpl_op_t op, int kernel) {
     case TPL_KERNEL_EXCHANGE_P2: {
       if (!op->dist) return 0.0;
       const double R = (double)op->dist->nranks;
-      if (op->hybrid) {  // per rank: n_long partials + its chunk alpha partials (y_ld1),
+      if (op->part.hybrid) {  // per rank: n_long partials + its chunk alpha partials (y_ld1),
         // then the norm total; pass two: n_long partials + 1
         const double nl = (double)op->lay.lrows.size();
         return kernel == TPL_KERNEL_EXCHANGE_P1 ? 8.0 * R * (op->y_ld1 + 1.0)
                                                 : 8.0 * R * (nl + 1.0);
       }
-      const double vec = (double)(op->halo ? op->hH : op->ld);
+      const double vec = (double)(op->part.halo ? op->part.hH : op->ld);
       // pass one: the alpha and beta totals and one vector part per rank (halo: its halo
       // slot); pass two: the vector part only (the row-block pass two gathers v, no totals)
       return kernel == TPL_KERNEL_EXCHANGE_P1 ? 8.0 * R * (vec + 2.0) : 8.0 * R * vec;
@@ -1977,9 +1749,9 @@ tpl_status tpl_profile_kernel(tpl_op_t op, int kernel, int iters, double* avg_us
     HIPCHK(launch::p1_init(A1, op->S, op->b, op->stream));
     HIPCHK(launch::p1_spmv(A1, op->S, op->bG, op->b, nullptr, op->W, nullptr, 1, op->stream));
     HIPCHK(launch::p1_axpy(A1, op->S, op->W, op->b, op->R[2], 1, big, 0, op->stream));
-    HIPCHK(hipMemcpyAsync(op->V2[1], op->b, op->n * sizeof(double), hipMemcpyDeviceToDevice,
+    HIPCHK(hipMemcpyAsync(op->V2[1], op->b, op->part.n * sizeof(double), hipMemcpyDeviceToDevice,
                           op->stream));
-    HIPCHK(hipMemcpyAsync(op->V2[2], op->R[2], op->n * sizeof(double), hipMemcpyDeviceToDevice,
+    HIPCHK(hipMemcpyAsync(op->V2[2], op->R[2], op->part.n * sizeof(double), hipMemcpyDeviceToDevice,
                           op->stream));
     HIPCHK(launch::p2_coefs(op->S, (int)op->kcap, 0, op->stream));  // step 2's record
     sync_checked(op);
@@ -2050,20 +1822,21 @@ tpl_status tpl_op_tune_order(tpl_op_t op, const int32_t* groups, int32_t count, 
     for (int32_t i = 0; i < cnt; ++i)
       if (list[i] <= 0) fail(TPL_ERR_INVALID_ARGUMENT, "group counts must be positive");
     // a failed timing launch leaves the operator as it was (order mode, group count)
-    const int saved_reorder = op->reorder, saved_groups = op->sp.order_groups;
+    const int saved_reorder = op->reorder;
+    const SchedParams saved_sp = op->sp;
     try {
-      op->reorder = 1;
+      SchedParams sp = op->sp;
       // any non-zero b: the timed SpMV launches need a step's valid partials and norms
       // (b is the solver's input staging buffer, re-written by every solve)
-      const std::vector<double> ones(op->n, 1.0);
+      const std::vector<double> unit(op->part.n, 1.0);
       double best = 0.0;
       int32_t best_g = op->sp.order_groups;
       for (int32_t i = 0; i < cnt; ++i) {
-        op->sp.order_groups = list[i];
-        rebuild_schedule(op);
+        sp.order_groups = list[i];
+        rebuild_schedule(op, sp, 1);
         if (op->perm.empty()) break;  // no long rows: nothing to order
-        if (op->n > 0)
-          HIPCHK(hipMemcpy(op->b, ones.data(), op->n * sizeof(double), hipMemcpyHostToDevice));
+        if (op->part.n > 0)
+          HIPCHK(hipMemcpy(op->b, unit.data(), op->part.n * sizeof(double), hipMemcpyHostToDevice));
         double t1 = 0.0, t2 = 0.0;
         for (const auto& kt : {std::make_pair(TPL_KERNEL_PASS1_SPMV, &t1),
                                std::make_pair(TPL_KERNEL_PASS2_SPMV, &t2)}) {
@@ -2075,15 +1848,13 @@ tpl_status tpl_op_tune_order(tpl_op_t op, const int32_t* groups, int32_t count, 
           best_g = list[i];
         }
       }
-      op->sp.order_groups = best_g;
-      rebuild_schedule(op);
+      sp.order_groups = best_g;
+      rebuild_schedule(op, sp, 1);
       if (chosen) *chosen = best_g;
       if (best_us) *best_us = best;
     } catch (...) {
-      op->reorder = saved_reorder;
-      op->sp.order_groups = saved_groups;
       hipGetLastError();
-      rebuild_schedule(op);
+      rebuild_schedule(op, saved_sp, saved_reorder);
       throw;
     }
   });
@@ -2096,8 +1867,9 @@ tpl_status tpl_op_set_order_groups(tpl_op_t op, int32_t groups) {
     if (op->dist) fail(TPL_ERR_UNSUPPORTED, "the locality order is single-GPU only");
     set_device(op);
     sync_checked(op);
-    op->sp.order_groups = groups > 0 ? groups : SchedParams{}.order_groups;
-    rebuild_schedule(op);
+    SchedParams sp = op->sp;
+    sp.order_groups = groups > 0 ? groups : SchedParams{}.order_groups;
+    rebuild_schedule(op, sp, op->reorder);
   });
 }
 
@@ -2111,11 +1883,7 @@ tpl_status tpl_dist_partition(int64_t n, const int64_t* row_ptr, int nranks, int
   return guarded([&] {
     if (!row_ptr || !starts || nranks < 1) fail(TPL_ERR_INVALID_ARGUMENT, "bad argument");
     if (n < nranks) fail(TPL_ERR_INVALID_ARGUMENT, "fewer rows than ranks");
-    // contiguous row blocks balanced by algorithmic bytes: 12 per nonzero (value +
-    // column) + 40 per row (pass two's vector traffic)
-    std::vector<double> prefix(n + 1);
-    for (int64_t i = 0; i <= n; ++i) prefix[i] = 12.0 * (double)row_ptr[i] + 40.0 * (double)i;
-    balanced_cuts(prefix, nranks, starts);
+    balanced_row_blocks(n, row_ptr, nranks, starts);
   });
 }
 
@@ -2181,32 +1949,9 @@ tpl_status tpl_dist_op_create_csr(tpl_dist_t d, int64_t n_global, const int64_t*
                                   const double* vals, tpl_op_t* out) {
   return guarded([&] {
     if (!d || !starts || !row_ptr || !out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
-    const int R = d->nranks;
-    if (starts[0] != 0 || starts[R] != n_global) fail(TPL_ERR_INVALID_ARGUMENT, "bad partition");
-    for (int r = 0; r < R; ++r)
-      if (starts[r + 1] <= starts[r]) fail(TPL_ERR_INVALID_ARGUMENT, "empty or unordered block");
-    if (n_global >= INT32_MAX / 2) fail(TPL_ERR_UNSUPPORTED, "n must be < 2^30");
-    const int64_t n = starts[d->rank + 1] - starts[d->rank];
-    const int64_t nnz = row_ptr[n];
-    if (row_ptr[0] != 0 || nnz < 0 || nnz >= INT32_MAX)
-      fail(TPL_ERR_INVALID_ARGUMENT, "row_ptr must start at 0; nnz < 2^31");
-    if (nnz > 0 && !vals) fail(TPL_ERR_INVALID_ARGUMENT, "col_idx/vals is NULL");
-    check_csr(n, n_global, row_ptr, col_idx);
+    RankPlan part = block_plan(d->nranks, d->rank, n_global, starts, row_ptr, col_idx, vals);
     HIPCHK(hipSetDevice(d->ctx.device));
-    auto op = std::make_unique<tpl_op_s>();
-    op->ctx = &d->ctx;
-    op->device = d->ctx.device;
-    op->stream = d->ctx.stream;
-    op->dist = d;
-    op->eager = d->comm == nullptr;
-    op->n = n;
-    op->n_glob = n_global;
-    op->nnz = nnz;
-    op->starts.assign(starts, starts + R + 1);
-    op->h_rowptr.resize(n + 1);
-    for (int64_t i = 0; i <= n; ++i) op->h_rowptr[i] = (int32_t)row_ptr[i];
-    op->h_col.assign(col_idx, col_idx + nnz);
-    op->h_val.assign(vals, vals + nnz);
+    auto op = make_op(&d->ctx, d, std::move(part));
     init_op(op.get());
     *out = op.release();
   });
@@ -2219,13 +1964,8 @@ tpl_status tpl_dist_op_create_halo(tpl_dist_t d, int64_t n, const int64_t* start
   return guarded([&] {
     if (!d || !row_ptr || !out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
     HIPCHK(hipSetDevice(d->ctx.device));
-    auto op = std::make_unique<tpl_op_s>();
-    op->ctx = &d->ctx;
-    op->device = d->ctx.device;
-    op->stream = d->ctx.stream;
-    op->dist = d;
-    op->eager = d->comm == nullptr;
-    fill_rows(op.get(), d->nranks, d->rank, n, starts, row_ptr, col_idx, vals, true);
+    const RowSplit s = split_rows(d->nranks, n, starts, row_ptr, col_idx, vals != nullptr, true);
+    auto op = make_op(&d->ctx, d, materialise(s, d->rank, row_ptr, col_idx, vals));
     init_op(op.get());
     *out = op.release();
   });
@@ -2237,13 +1977,9 @@ tpl_status tpl_dist_op_create_replicated(tpl_dist_t d, int64_t n, const int64_t*
   return guarded([&] {
     if (!d || !row_ptr || !out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
     HIPCHK(hipSetDevice(d->ctx.device));
-    auto op = std::make_unique<tpl_op_s>();
-    op->ctx = &d->ctx;
-    op->device = d->ctx.device;
-    op->stream = d->ctx.stream;
-    op->dist = d;
-    op->eager = d->comm == nullptr;
-    fill_replicated(op.get(), d->nranks, d->rank, n, row_ptr, col_idx, vals);
+    const ReplicatedSplit s = split_replicated(d->nranks, n, row_ptr, col_idx, vals != nullptr);
+    if (!s.feasible()) fail(TPL_ERR_UNSUPPORTED, s.refused);
+    auto op = make_op(&d->ctx, d, materialise(s, d->rank, row_ptr, col_idx, vals));
     init_op(op.get());
     *out = op.release();
   });
@@ -2253,7 +1989,7 @@ tpl_status tpl_dist_choose_partition(int64_t n, const int64_t* row_ptr, const in
                                      int nranks, int* mode) {
   return guarded([&] {
     if (!mode) fail(TPL_ERR_INVALID_ARGUMENT, "mode is NULL");
-    *mode = choose_partition(n, row_ptr, col_idx, nranks);
+    *mode = choose_partition(n, row_ptr, col_idx, nranks).mode;
   });
 }
 
@@ -2262,21 +1998,14 @@ tpl_status tpl_dist_op_create_auto(tpl_dist_t d, int64_t n, const int64_t* row_p
                                    int* mode) {
   return guarded([&] {
     if (!d || !row_ptr || !out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
-    const int m = choose_partition(n, row_ptr, col_idx, d->nranks);
+    const PartitionChoice c = choose_partition(n, row_ptr, col_idx, d->nranks);
     HIPCHK(hipSetDevice(d->ctx.device));
-    auto op = std::make_unique<tpl_op_s>();
-    op->ctx = &d->ctx;
-    op->device = d->ctx.device;
-    op->stream = d->ctx.stream;
-    op->dist = d;
-    op->eager = d->comm == nullptr;
-    if (m == TPL_PLAN_REPLICATED)
-      fill_replicated(op.get(), d->nranks, d->rank, n, row_ptr, col_idx, vals);
-    else
-      fill_rows(op.get(), d->nranks, d->rank, n, nullptr, row_ptr, col_idx, vals,
-                m == TPL_PLAN_HALO);
+    if (row_ptr[n] > 0 && !vals) fail(TPL_ERR_INVALID_ARGUMENT, "col_idx/vals is NULL");
+    auto op = make_op(&d->ctx, d, c.mode == TPL_PLAN_REPLICATED
+                                      ? materialise(c.rep, d->rank, row_ptr, col_idx, vals)
+                                      : materialise(c.rows, d->rank, row_ptr, col_idx, vals));
     init_op(op.get());
-    if (mode) *mode = m;
+    if (mode) *mode = c.mode;
     *out = op.release();
   });
 }
@@ -2320,11 +2049,11 @@ tpl_status tpl_operand_key(int64_t n, const void* ptr_arr, size_t ptr_len, size_
 tpl_status tpl_op_local_rows(tpl_op_t op, int64_t* rows) {
   return guarded([&] {
     if (!op || !rows) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (op->hybrid) {
-      std::copy(op->local_rows.begin(), op->local_rows.end(), rows);
+    if (op->part.hybrid) {
+      std::copy(op->part.local_rows.begin(), op->part.local_rows.end(), rows);
     } else {
-      const int64_t r0 = op->dist ? op->starts[op->dist->rank] : 0;
-      for (int64_t i = 0; i < op->n; ++i) rows[i] = r0 + i;
+      const int64_t r0 = op->dist ? op->part.starts[op->dist->rank] : 0;
+      for (int64_t i = 0; i < op->part.n; ++i) rows[i] = r0 + i;
     }
   });
 }
@@ -2345,33 +2074,30 @@ tpl_status tpl_plan_create(int64_t n, const int64_t* row_ptr, const int32_t* col
     if (n < 0) fail(TPL_ERR_INVALID_ARGUMENT, "negative size");
     const int64_t nnz = row_ptr[n];
     if (nnz > 0 && (!vals || !col_idx)) fail(TPL_ERR_INVALID_ARGUMENT, "col_idx/vals is NULL");
-    auto op = std::make_unique<tpl_op_s>();
-    op->plan_only = true;
+    std::unique_ptr<tpl_dist_s> pd;  // a partitioned plan's rank and rank count
+    RankPlan part;
     if (mode == TPL_PLAN_SINGLE) {  // tpl_op_create_csr's host half
-      if (n >= INT32_MAX || nnz >= INT32_MAX)
-        fail(TPL_ERR_UNSUPPORTED, "n and nnz must be < 2^31 (int32 device offsets)");
-      check_csr(n, n, row_ptr, col_idx);
-      op->n = op->n_glob = n;
-      op->nnz = nnz;
-      op->h_rowptr.assign(row_ptr, row_ptr + n + 1);
-      op->h_col.assign(col_idx, col_idx + nnz);
-      op->h_val.assign(vals, vals + nnz);
-      if (order_groups > 0) op->sp.order_groups = order_groups;
+      part = single_plan(n, nnz, row_ptr, col_idx, vals);
     } else {
-      op->plan_dist = std::make_unique<tpl_dist_s>();
-      op->plan_dist->rank = rank;
-      op->plan_dist->nranks = nranks;
-      op->dist = op->plan_dist.get();
+      pd = std::make_unique<tpl_dist_s>();
+      pd->rank = rank;
+      pd->nranks = nranks;
       if (mode == TPL_PLAN_REPLICATED) {
-        fill_replicated(op.get(), nranks, rank, n, row_ptr, col_idx, vals);
+        const ReplicatedSplit s = split_replicated(nranks, n, row_ptr, col_idx);
+        if (!s.feasible()) fail(TPL_ERR_UNSUPPORTED, s.refused);
+        part = materialise(s, rank, row_ptr, col_idx, vals);
       } else {  // the block tpl_dist_partition gives this rank (tpl_dist_op_create_csr /
                 // tpl_dist_op_create_halo)
-        fill_rows(op.get(), nranks, rank, n, nullptr, row_ptr, col_idx, vals,
-                  mode == TPL_PLAN_HALO);
+        const bool halo = mode == TPL_PLAN_HALO;
+        part = materialise(split_rows(nranks, n, nullptr, row_ptr, col_idx, true, halo), rank,
+                           row_ptr, col_idx, vals);
       }
     }
+    auto op = make_op(nullptr, pd.get(), std::move(part));
+    op->plan_dist = std::move(pd);
+    if (mode == TPL_PLAN_SINGLE && order_groups > 0) op->sp.order_groups = order_groups;
     set_stride(op.get());
-    rebuild_schedule(op.get());  // the layout only (plan_only: nothing is uploaded)
+    rebuild_schedule(op.get(), op->sp, op->reorder);  // the layout only: nothing is uploaded
     *out = op.release();
   });
 }
