@@ -205,4 +205,86 @@ struct DevState {
   const double* Pb_r;
 };
 
+// Kernel arguments of the pass-one step kernels: the fields of CsrDev, DevState and the
+// launch those kernels read, and nothing else, so that the compiler fetches all of them in
+// one batch of wide scalar loads at entry (whole CsrDev + DevState by value made a
+// 376 / 624-byte segment whose loads came in up to three dependent batches). Filled by the
+// launchers (tpl::launch::p1_spmv / p1_axpy) at each launch, i.e. when the pass graph is
+// captured. Field order: what the short-chunk path reads first, then the bins', then the rest;
+// fields read together are adjacent, so they arrive in a few wide loads.
+struct P1SpmvArgs {
+  // every path: the step's vectors and coefficients
+  const double* Pb_r;       // DevState
+  int32_t* flags;
+  double* norms;
+  double* betas;
+  double* Pa;
+  const double* xsrc;
+  const double* r_cur;
+  const double* r_prev;
+  double* W;
+  double* Vcol;
+  unsigned long long* stamp;
+  // short chunks
+  const void* s_col;        // CsrDev, as named there
+  const void* s_val;
+  const int32_t* s_cbase;
+  const int32_t* srows;
+  int64_t E;
+  int32_t j;
+  int32_t G2;
+  int32_t G2_r;
+  int32_t n_slice_blocks;
+  int32_t n_chunks;
+  int32_t n_short;
+  int32_t s_identity;
+  int32_t n_slices;
+  // bins
+  int32_t bin_cap;
+  int32_t s_width;          // (generic chunk width, with c_base / c_width)
+  const void* b_col;
+  const void* b_val;
+  const int32_t* b_cbase;
+  const BinSeg* b_seg;
+  const int32_t* b_hdr;
+  // the generic chunk width, the column window, the gathered norm partials
+  const int32_t* c_base;
+  const int32_t* c_width;
+  int32_t s_win;
+  int32_t s_win_max;
+  int32_t pb_ld;
+  // the long rows' hand-off, read at the end of a bin behind its entries and gathers: kept
+  // apart from the fields above so that the entry batch does not fetch them too (with them
+  // k_p1_spmv<58> holds 82 SGPRs at its first wait, 76 without)
+  int32_t long_defer;
+  double* P;
+  unsigned int* Pcnt;
+  double* ypart;
+};
+
+struct P1AxpyArgs {
+  const double* Pa_r;       // DevState
+  const double* W;
+  const double* r_cur;
+  double* r_next;
+  int32_t* flags;
+  double* norms;
+  double* alphas;
+  double* Pb;
+  unsigned long long* stamp;
+  int64_t n;                // CsrDev
+  int64_t E;
+  int64_t norm_n;
+  int32_t NA_r;
+  int32_t G2;
+  int32_t j;
+  int32_t k;
+  int32_t elim_block;       // the elimination workgroup's block index (one-graph inv): the
+                            // block after the element grid, padding blocks included; -1: none
+  // read by the elimination workgroup only
+  int32_t kcap;
+  double* betas;
+  double* lu;
+};
+
 } // namespace tpl

@@ -740,11 +740,12 @@ __device__ __forceinline__ void long_bin(const CsrDev& A, int m, int s,
 // against 2048-row blocks dealt round-robin.
 __device__ __forceinline__ int rb_first(int G2, int x) { return (x * G2 + 7) >> 3; }
 // element-wise grid (8 ceil(G2 / 8) blocks): block i -> row block, or -1 (padding)
-__device__ __forceinline__ int elem_block(const CsrDev& A, int i) {
+__device__ __forceinline__ int elem_block(int G2, int i) {
   const int x = i & 7, q = i >> 3;
-  const int rb = rb_first(A.G2, x) + q;
-  return rb < rb_first(A.G2, x + 1) ? rb : -1;
+  const int rb = rb_first(G2, x) + q;
+  return rb < rb_first(G2, x + 1) ? rb : -1;
 }
+__device__ __forceinline__ int elem_block(const CsrDev& A, int i) { return elem_block(A.G2, i); }
 // chunk part of an SpMV grid: block i of the part -> short chunk, or -1 (padding)
 __device__ __forceinline__ int chunk_of_block(const CsrDev& A, int i) {
   const int cpe = (int)(A.E / kChunkRows);  // chunks per row block

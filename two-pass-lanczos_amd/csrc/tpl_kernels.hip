@@ -36,6 +36,8 @@ template <int F>
 __global__ __launch_bounds__(kTPB, kSpmvMinWaves) void k_spmv(CsrDev A, const double* __restrict__ x,
                                                double* __restrict__ y) {
   extern __shared__ double lds[];
+  pin_layout_args(A);
+  asm volatile("" ::"s"(A.E), "s"(A.G2), "s"(A.srows), "s"(x), "s"(y));
   double acc = 0.0;
   spmv_block<F>(A, x, UnitScale{}, EpiSpmv{y}, acc, lds);
 }
@@ -88,19 +90,48 @@ __global__ __launch_bounds__(kTPB) void k_p1_init(CsrDev A, DevState S,
 constexpr int p1_min_waves(int F, int NBP) {
   return (NBP > 1 && (F & 8) && ((F & 7) == 1 || (F & 7) == 2)) ? 6 : kSpmvMinWaves;
 }
+// The SpMV building blocks (tpl_kcommon.h) read the layout through a CsrDev: the view of
+// the fields the kernel argument carries. The fields no SpMV path reads stay zero and are
+// never materialised (every user is inlined).
+__device__ __forceinline__ CsrDev layout_of(const P1SpmvArgs& a) {
+  CsrDev A{};
+  A.srows = a.srows; A.s_col = a.s_col; A.s_cbase = a.s_cbase; A.s_val = a.s_val;
+  A.c_base = a.c_base; A.c_width = a.c_width;
+  A.b_col = a.b_col; A.b_cbase = a.b_cbase; A.b_val = a.b_val; A.b_seg = a.b_seg;
+  A.b_hdr = a.b_hdr; A.P = a.P; A.Pcnt = a.Pcnt;
+  A.s_width = a.s_width; A.s_identity = a.s_identity; A.n_short = a.n_short;
+  A.n_chunks = a.n_chunks; A.bin_cap = a.bin_cap; A.n_slice_blocks = a.n_slice_blocks;
+  A.G2 = a.G2; A.G2_r = a.G2_r; A.pb_ld = a.pb_ld; A.n_slices = a.n_slices; A.E = a.E;
+  A.ypart = a.ypart; A.long_defer = a.long_defer; A.s_win = a.s_win;
+  A.s_win_max = a.s_win_max;
+  return A;
+}
 template <int F, int NBP>
-__device__ __forceinline__ void p1_spmv_body(const CsrDev& A, const DevState& S,
-                                             const double* __restrict__ xsrc,
-                                             const double* __restrict__ r_cur,
-                                             const double* __restrict__ r_prev,
-                                             double* __restrict__ W, double* __restrict__ Vcol,
-                                             int j, unsigned long long* stamp, double* red,
-                                             double* redb, double* lds,
-                                             double* redr = nullptr) {
-  // every kernel argument in ONE scalar round trip, the launch stamp's pointer included:
-  // a branch on an argument before this point (the stamp test) split the loads into three
-  // dependent round trips ahead of the first vector load (ISA, round 6)
+__device__ __forceinline__ void p1_spmv_body(const P1SpmvArgs& a, double* red, double* redb,
+                                             double* lds, double* redr = nullptr) {
+  // Every kernel argument a path reads ahead of its first vector load is fetched by the
+  // entry batch of scalar loads, before any branch on one of them (hipcc sinks an
+  // argument's load into the branch that uses it: a dependent scalar round trip there).
+  // The layout fields, E and G2 (chunk_of_block) included, and the launch stamp's pointer;
+  // scripts/entry_trips.py checks the compiled code for loads behind the first wait. Left
+  // to load where they are used, behind the bin's vector loads: the hand-off's fields (P,
+  // Pcnt, long_defer, ypart) — fetched at entry as well they take k_p1_spmv<58> to 82 SGPRs.
+  const CsrDev A = layout_of(a);
+  struct {
+    const double* Pb_r; int32_t* flags; double* norms; double* betas; double* Pa;
+  } S{a.Pb_r, a.flags, a.norms, a.betas, a.Pa};
+  const double* __restrict__ xsrc = a.xsrc;
+  const double* __restrict__ r_cur = a.r_cur;
+  const double* __restrict__ r_prev = a.r_prev;
+  double* __restrict__ W = a.W;
+  double* __restrict__ Vcol = a.Vcol;
+  const int j = a.j;
+  unsigned long long* stamp = a.stamp;
   pin_layout_args(A);
+  asm volatile("" ::"s"(A.E), "s"(A.G2), "s"(A.srows));
+  if constexpr ((F & 7) == 0) asm volatile("" ::"s"(A.c_base), "s"(A.c_width), "s"(A.s_width));
+  if constexpr ((F & 64) != 0) asm volatile("" ::"s"(A.s_win), "s"(A.s_win_max));
+  if constexpr (NBP < 0) asm volatile("" ::"s"(A.pb_ld));
   asm volatile("" ::"s"(S.Pb_r), "s"(S.flags), "s"(S.norms), "s"(S.betas), "s"(S.Pa), "s"(A.G2_r),
                "s"(xsrc), "s"(r_cur), "s"(r_prev), "s"(W), "s"(Vcol), "s"(j), "s"(stamp));
   launch_stamp(stamp);
@@ -204,45 +235,26 @@ __device__ __forceinline__ void p1_spmv_body(const CsrDev& A, const DevState& S,
 }
 // G2_r <= 256 norm partials (one per thread) ...
 template <int F>
-__global__ __launch_bounds__(kTPB, p1_min_waves(F, 1)) void k_p1_spmv(CsrDev A, DevState S,
-                                                  const double* __restrict__ xsrc,
-                                                  const double* __restrict__ r_cur,
-                                                  const double* __restrict__ r_prev,
-                                                  double* __restrict__ W,
-                                                  double* __restrict__ Vcol, int j,
-                                                  unsigned long long* stamp) {
+__global__ __launch_bounds__(kTPB, p1_min_waves(F, 1)) void k_p1_spmv(P1SpmvArgs a) {
   TPL_MARK_FIRST();
   __shared__ double red[4], redb[4];
   extern __shared__ double lds[];
-  p1_spmv_body<F, 1>(A, S, xsrc, r_cur, r_prev, W, Vcol, j, stamp, red, redb, lds);
+  p1_spmv_body<F, 1>(a, red, redb, lds);
 }
 // ... every rank's norm partials, gathered (replicated partition: CsrDev::pb_ld) ...
 template <int F>
-__global__ __launch_bounds__(kTPB, p1_min_waves(F, 1)) void k_p1_spmv_gp(CsrDev A, DevState S,
-                                                  const double* __restrict__ xsrc,
-                                                  const double* __restrict__ r_cur,
-                                                  const double* __restrict__ r_prev,
-                                                  double* __restrict__ W,
-                                                  double* __restrict__ Vcol, int j,
-                                                  unsigned long long* stamp) {
+__global__ __launch_bounds__(kTPB, p1_min_waves(F, 1)) void k_p1_spmv_gp(P1SpmvArgs a) {
   __shared__ double red[4], redb[4], redr[4 * kPbRanks];
   extern __shared__ double lds[];
-  p1_spmv_body<F, -kPbRanks>(A, S, xsrc, r_cur, r_prev, W, Vcol, j, stamp, red, redb, lds,
-                             redr);
+  p1_spmv_body<F, -kPbRanks>(a, red, redb, lds, redr);
 }
 // ... and more (four per thread first, the rest in batches; the 5M-arc instance's 1,024
 // row blocks)
 template <int F>
-__global__ __launch_bounds__(kTPB, p1_min_waves(F, 4)) void k_p1_spmv_wide(CsrDev A, DevState S,
-                                                  const double* __restrict__ xsrc,
-                                                  const double* __restrict__ r_cur,
-                                                  const double* __restrict__ r_prev,
-                                                  double* __restrict__ W,
-                                                  double* __restrict__ Vcol, int j,
-                                                  unsigned long long* stamp) {
+__global__ __launch_bounds__(kTPB, p1_min_waves(F, 4)) void k_p1_spmv_wide(P1SpmvArgs a) {
   __shared__ double red[4], redb[4];
   extern __shared__ double lds[];
-  p1_spmv_body<F, 4>(A, S, xsrc, r_cur, r_prev, W, Vcol, j, stamp, red, redb, lds);
+  p1_spmv_body<F, 4>(a, red, redb, lds);
 }
 
 // ---- T_k^{-1} e_1 on the device (the one-graph inv): the host solver's operations
@@ -311,48 +323,66 @@ __device__ __forceinline__ double div_rn(double a, double b, double y, bool b_ok
 // NP: alpha partials loaded per thread up front (the launcher picks the smallest of 2, 4,
 // 8, 12 with 256 NP >= NA_r; more are reduced in batches): clamped duplicate loads of a
 // small partial array only cost issue slots and cache traffic.
-// elim (one-graph inv): one more workgroup (the last) eliminates row j - 3 of T_k's LU
+// elim (one-graph inv): one more workgroup eliminates row j - 3 of T_k's LU
 // (lu_row): its inputs beta_{j-3}, alpha_{j-2} and beta_{j-2} (0-based) are all known
 // once this step's k_p1_spmv has reduced beta — the row is done off the critical path,
 // so only the last rows and the back substitution remain after pass one (k_ftk_inv).
+// That workgroup is block a.elim_block, the one after the element grid (its padding
+// blocks included, so never one elem_block maps to a row block or to -1); -1: none.
 template <int NP>
-__global__ __launch_bounds__(kTPB) void k_p1_axpy(CsrDev A, DevState S,
-                                                  const double* __restrict__ W,
-                                                  const double* __restrict__ r_cur,
-                                                  double* __restrict__ r_next, int j, int k,
-                                                  int elim, unsigned long long* stamp) {
+__global__ __launch_bounds__(kTPB) void k_p1_axpy(P1AxpyArgs a) {
   __shared__ double red[4];
-  // every kernel argument in ONE scalar round trip before any branch on one of them (the
-  // stamp and elim tests used to split the loads into three dependent round trips ahead of
-  // the first vector load: ISA, round 6)
-  asm volatile("" ::"s"(A.E), "s"(A.n), "s"(A.norm_n), "s"(A.NA_r), "s"(S.Pa_r), "s"(S.flags),
-               "s"(S.norms), "s"(S.alphas), "s"(S.Pb));
-  asm volatile("" ::"s"(W), "s"(r_cur), "s"(r_next), "s"(j), "s"(k), "s"(elim), "s"(stamp));
+  // Every kernel argument the element blocks read is fetched by the entry batch of scalar
+  // loads, before any branch on one of them: a test of the stamp pointer, of gridDim.x
+  // (a hidden argument) or of G2 ahead of the vector loads each cost a dependent scalar
+  // round trip (ISA; scripts/entry_trips.py checks the compiled code). Only the
+  // elimination workgroup's own fields (lu, kcap, betas) load later, on its branch.
+  struct {
+    int64_t E, n, norm_n; int NA_r, G2;
+  } A{a.E, a.n, a.norm_n, a.NA_r, a.G2};
+  struct {
+    const double* Pa_r; int32_t* flags; double* norms; double* alphas; double* Pb;
+  } S{a.Pa_r, a.flags, a.norms, a.alphas, a.Pb};
+  const double* __restrict__ W = a.W;
+  const double* __restrict__ r_cur = a.r_cur;
+  double* __restrict__ r_next = a.r_next;
+  const int j = a.j, k = a.k, elim_block = a.elim_block;
+  unsigned long long* stamp = a.stamp;
+  asm volatile("" ::"s"(A.E), "s"(A.n), "s"(A.norm_n), "s"(A.NA_r), "s"(A.G2), "s"(S.Pa_r),
+               "s"(S.flags), "s"(S.norms), "s"(S.alphas), "s"(S.Pb));
+  asm volatile("" ::"s"(W), "s"(r_cur), "s"(r_next), "s"(j), "s"(k), "s"(elim_block),
+               "s"(stamp));
   launch_stamp(stamp);
-  if (elim && blockIdx.x == gridDim.x - 1) {
+  if ((int)blockIdx.x == elim_block) {
     if (threadIdx.x != 0 || j < 3) return;
     const int i = j - 3;
-    double* D = S.lu;
-    double* st = S.lu + 4 * (size_t)S.kcap;
+    const size_t kcap = (size_t)a.kcap;
+    double* D = a.lu;
+    double* st = a.lu + 4 * kcap;
     // every input with the flags (one round trip): the row's coefficients and the running
     // row (the initial one at i = 0: alpha_0, beta_0, 1)
     const int stop = S.flags[0], done = S.flags[5];
-    const double dli = S.betas[i], d1 = S.alphas[i + 1], du1 = S.betas[i + 1];
+    const double dli = a.betas[i], d1 = S.alphas[i + 1], du1 = a.betas[i + 1];
     LuRow cur{st[0], st[1], st[2]};
     const double a0 = S.alphas[0];
     if (stop || done != i) return;  // breakdown at this step: the tail finishes the rows
     if (i == 0) cur = LuRow{a0, dli, 1.0};
-    lu_row(i, true, dli, d1, du1, cur, D, D + S.kcap, D + 2 * (size_t)S.kcap,
-           D + 3 * (size_t)S.kcap);
+    lu_row(i, true, dli, d1, du1, cur, D, D + kcap, D + 2 * kcap, D + 3 * kcap);
     st[0] = cur.d;
     st[1] = cur.du;
     st[2] = cur.b;
     S.flags[5] = i + 1;
     return;
   }
-  const int rb = elem_block(A, blockIdx.x);
+  const int rb = elem_block(A.G2, blockIdx.x);
   if (rb < 0) return;
   TPL_MARK_AT(kAxpyMarkBase, 0);
+  // The DevState scalars (stop flag, ||r_j||) are the first loads issued (vector loads at a
+  // uniform address: no scalar round trip), so that 1 / ||r_j|| can be taken while the
+  // alpha partials and the vectors are still in flight (below).
+  const int stop = S.flags[0];
+  const double normj = S.norms[j - 1];
+  __builtin_amdgcn_sched_barrier(0);
   PartialRegs<NP> pr;
   const int na_ = A.NA_r;
   load_partials(S.Pa_r, na_, pr);
@@ -372,12 +402,16 @@ __global__ __launch_bounds__(kTPB) void k_p1_axpy(CsrDev A, DevState S,
     w0[q] = *reinterpret_cast<const double2*>(W + ic);
     rc0[q] = *reinterpret_cast<const double2*>(r_cur + ic);
   }
-  // The DevState scalars (stop flag, ||r_j||) are read only now, with the vector loads
-  // in flight: waited on at entry they would add a dependent round trip.
+  // 1 / ||r_j|| now, off the chain that follows alpha: the division is about ten
+  // dependent FP64 operations, and its wait (vmcnt counts down in issue order) covers the
+  // two loads above only, not the partials or the vectors. Same operation, same operand:
+  // the same bits as dividing after the reduction (same box, alternated three times: solve
+  // 8.04 vs 8.13-8.15 ms, pass one 9.99-10.03 vs 10.22-10.29 us per step).
   __builtin_amdgcn_sched_barrier(0);
-  const int stop = S.flags[0];
-  const double normj = S.norms[j - 1];
   TPL_MARK_AT(kAxpyMarkBase, 1);
+  double invN = 1.0 / normj;
+  keep(invN);
+  __builtin_amdgcn_sched_barrier(0);
 #if TPL_STAMP
   // diagnostic build: when the alpha partials (issued first) have landed, the vector loads
   // (2 kAxPairs issued after them) still in flight
@@ -396,7 +430,6 @@ __global__ __launch_bounds__(kTPB) void k_p1_axpy(CsrDev A, DevState S,
     S.flags[2] = j;
   }
   if (j == k) return; // beta_k is never used (src/algorithms/lanczos_two_pass.rs:252-254)
-  const double invN = 1.0 / normj;
   double acc = 0.0;
   auto step = [&](int64_t i0, double2 w, double2 rc) {
     double2 r;
@@ -1372,25 +1405,40 @@ hipError_t p1_spmv(const CsrDev& A, const DevState& S, const double* xsrc, const
                    const double* r_prev, double* W, double* Vcol, int j, hipStream_t s,
                    unsigned long long* stamp) {
   if (spmv_grid(A) <= 0) return hipGetLastError();
-  if (A.pb_ld > 0)
-    return TPL_LAUNCH_CW(k_p1_spmv_gp, A, s, A, S, xsrc, r_cur, r_prev, W, Vcol, j, stamp);
-  if (A.G2_r <= kTPB)
-    return TPL_LAUNCH_CW(k_p1_spmv, A, s, A, S, xsrc, r_cur, r_prev, W, Vcol, j, stamp);
-  return TPL_LAUNCH_CW(k_p1_spmv_wide, A, s, A, S, xsrc, r_cur, r_prev, W, Vcol, j, stamp);
-  return hipGetLastError();
+  P1SpmvArgs a{};
+  a.Pb_r = S.Pb_r; a.flags = S.flags; a.norms = S.norms; a.betas = S.betas; a.Pa = S.Pa;
+  a.xsrc = xsrc; a.r_cur = r_cur; a.r_prev = r_prev; a.W = W; a.Vcol = Vcol; a.stamp = stamp;
+  a.s_col = A.s_col; a.s_val = A.s_val; a.s_cbase = A.s_cbase; a.srows = A.srows;
+  a.E = A.E; a.j = j; a.G2 = A.G2; a.G2_r = A.G2_r; a.n_slice_blocks = A.n_slice_blocks;
+  a.n_chunks = A.n_chunks; a.n_short = A.n_short; a.s_identity = A.s_identity;
+  a.n_slices = A.n_slices; a.bin_cap = A.bin_cap; a.long_defer = A.long_defer;
+  a.b_col = A.b_col; a.b_val = A.b_val; a.b_cbase = A.b_cbase; a.b_seg = A.b_seg;
+  a.b_hdr = A.b_hdr; a.P = A.P; a.Pcnt = A.Pcnt; a.ypart = A.ypart;
+  a.c_base = A.c_base; a.c_width = A.c_width; a.s_width = A.s_width; a.s_win = A.s_win;
+  a.s_win_max = A.s_win_max; a.pb_ld = A.pb_ld;
+  if (A.pb_ld > 0) return TPL_LAUNCH_CW(k_p1_spmv_gp, A, s, a);
+  if (A.G2_r <= kTPB) return TPL_LAUNCH_CW(k_p1_spmv, A, s, a);
+  return TPL_LAUNCH_CW(k_p1_spmv_wide, A, s, a);
 }
 hipError_t p1_axpy(const CsrDev& A, const DevState& S, const double* W, const double* r_cur,
                    double* r_next, int j, int k, int elim, hipStream_t s,
                    unsigned long long* st) {
+  P1AxpyArgs a{};
+  a.Pa_r = S.Pa_r; a.W = W; a.r_cur = r_cur; a.r_next = r_next; a.flags = S.flags;
+  a.norms = S.norms; a.alphas = S.alphas; a.Pb = S.Pb; a.stamp = st;
+  a.n = A.n; a.E = A.E; a.norm_n = A.norm_n; a.NA_r = A.NA_r; a.G2 = A.G2; a.j = j; a.k = k;
+  // the elimination workgroup: the block after the element grid, padding blocks included
+  a.elim_block = elim ? g2_grid(A) : -1;
+  a.kcap = S.kcap; a.betas = S.betas; a.lu = S.lu;
   const dim3 g(g2_grid(A) + (elim ? 1 : 0)), b(kTPB);
   if (A.NA_r <= 2 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy<2>, g, b, 0, s, A, S, W, r_cur, r_next, j, k, elim, st);
+    hipLaunchKernelGGL(k_p1_axpy<2>, g, b, 0, s, a);
   else if (A.NA_r <= 4 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy<4>, g, b, 0, s, A, S, W, r_cur, r_next, j, k, elim, st);
+    hipLaunchKernelGGL(k_p1_axpy<4>, g, b, 0, s, a);
   else if (A.NA_r <= 8 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy<8>, g, b, 0, s, A, S, W, r_cur, r_next, j, k, elim, st);
+    hipLaunchKernelGGL(k_p1_axpy<8>, g, b, 0, s, a);
   else
-    hipLaunchKernelGGL(k_p1_axpy<12>, g, b, 0, s, A, S, W, r_cur, r_next, j, k, elim, st);
+    hipLaunchKernelGGL(k_p1_axpy<12>, g, b, 0, s, a);
   return hipGetLastError();
 }
 hipError_t p2_init(int64_t n, const DevState& S, const double* b, double* v1, double* x,
