@@ -102,7 +102,7 @@ static void spmv_faithful(const ocsr* A, const double* x, double* y) {
  * form a piece; a piece of at most BIG_PIECE entries: lane g (0..7) sums its entries
  * g + 8q, butterfly over the 8 lanes (xor 1, 2, 4); a longer piece: lane g (0..15) sums
  * its entries g + 16q, butterfly over 16 lanes. -> P_s; y = 0; y += P_s (s ascending). S: the
- * schedule's slice count (tpl_runtime.cpp auto_slices).
+ * schedule's slice count (tpl_layout.cpp auto_slices).
  * (device: long_bin in tpl_kernels.hip; kBigPiece in tpl_device.h) */
 #define BIG_PIECE 64
 static double long_row_canon(const ocsr* A, int32_t i, const double* x, int S) {

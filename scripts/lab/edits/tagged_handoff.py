@@ -9,18 +9,16 @@ assert a in s
 s = s.replace(a, '#define TPL_SLOT_STRIDE (2 * TPL_MAX_SLICES)')
 open('tpl_device.h', 'w').write(s)
 
-s = open('tpl_runtime.cpp').read()
-a = '''  upload(op, &op->d_P, std::vector<double>(std::max<size_t>(L.lrows.size() * kSlotStride, 1), 0.0));'''
+s = open('tpl_operator.cpp').read()  # tpl_op.h brings <cstring>
+a = '''  upload(op, &nb.d_P, std::vector<double>(std::max<size_t>(L.lrows.size() * kSlotStride, 1), 0.0));'''
 assert a in s
 s = s.replace(a, '''  {
     double ones;
     const unsigned long long u = ~0ull;
     std::memcpy(&ones, &u, sizeof ones);
-    upload(op, &op->d_P, std::vector<double>(std::max<size_t>(L.lrows.size() * kSlotStride, 1), ones));
+    upload(op, &nb.d_P, std::vector<double>(std::max<size_t>(L.lrows.size() * kSlotStride, 1), ones));
   }''')
-if '#include <cstring>' not in s:
-    s = s.replace('#include <algorithm>', '#include <algorithm>\n#include <cstring>', 1)
-open('tpl_runtime.cpp', 'w').write(s)
+open('tpl_operator.cpp', 'w').write(s)
 
 s = open('tpl_kcommon.h').read()
 a = '''  // the finalising thread's own row entries travel with the gathers

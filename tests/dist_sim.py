@@ -1,5 +1,5 @@
 """Host simulation of the row-partitioned two-pass Lanczos exchange protocol (the one
-tpl_runtime.cpp runs over RCCL): test infrastructure for the world_size > 1 CPU tests.
+tpl_dist.cpp runs over RCCL): test infrastructure for the world_size > 1 CPU tests.
 
 Each rank owns rows [starts[r], starts[r+1]) (tpl_dist_partition), keeps only its
 block of every vector, all-gathers the vector before each SpMV, and forms alpha and

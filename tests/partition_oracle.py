@@ -1,7 +1,7 @@
 """Partitioned reduction orders of the multi-GPU operator, restated on the CPU — TEST
 INFRASTRUCTURE (composes the C oracle's primitives; never on the product path).
 
-The row-partitioned solve (tpl_runtime.cpp) keeps alpha, beta and x
+The row-partitioned solve (tpl_dist.cpp and tpl_passes.cpp) keeps alpha, beta and x
 bitwise identical on every rank because each rank reduces its own partials in the
 single-GPU canonical order and the R rank totals are combined in rank order. This
 module replays exactly that, given each rank's layout (HipCsrOp.schedule() on that rank),

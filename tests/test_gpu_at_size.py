@@ -270,8 +270,8 @@ def test_config4_5m_partitions_two_ranks(tmp_path, mode, op5m, kkt5m):
 
 @pytest.mark.timeout(600)
 def test_replicated_wide_blocks_two_ranks(tmp_path):
-    """The replicated partition's widened element-wise blocks (tpl_runtime.cpp
-    fill_replicated: at most 256 norm partials per rank when that needs <= 4,096 rows per
+    """The replicated partition's widened element-wise blocks (tpl_partition.cpp
+    split_replicated: at most 256 norm partials per rank when that needs <= 4,096 rows per
     block — configs[4] at N = 8): a 1.5M-arc synthetic instance over two ranks holds
     ~750k rows per rank, 367 partials at the default 2,048 rows, so the rule widens the
     blocks to 3,072 rows (245 partials) and pass one's SpMV reduces the gathered partials

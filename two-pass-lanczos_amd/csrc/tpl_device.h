@@ -1,8 +1,8 @@
 // tpl_device.h — structures shared by the HIP kernels (tpl_kernels.hip) and the
-// host runtime (tpl_runtime.cpp). Everything here is plain data: the kernels take
+// host units (tpl_op.h). Everything here is plain data: the kernels take
 // these structs by value as kernel arguments.
 //
-// SpMV layout (built once per operator, tpl_runtime.cpp build_layout):
+// SpMV layout (built once per operator, tpl_layout.cpp build_layout):
 //   * SHORT rows (<= T nnz, T = clamp(2 * median row nnz, 4, kShortRowMax) unless
 //     set explicitly), taken in ascending order, are stored as sliced ELL: chunk c
 //     holds short-row positions [C*c, C*c + C) (C = kChunkRows); entry k of position
@@ -12,7 +12,7 @@
 //     pointer is chased. When every chunk has the same width W the chunk bases are
 //     computed, not loaded, and the kernel is specialised for W.
 //   * LONG rows are cut into S column slices [floor(n*s/S), floor(n*(s+1)/S)), S in
-//     {1, 2, 4, 8} (tpl_runtime.cpp auto_slices: the fewest whose share of the
+//     {1, 2, 4, 8} (tpl_layout.cpp auto_slices: the fewest whose share of the
 //     gathered vector fits an eighth of an L2). The (row, slice) pieces of slice s that
 //     hold entries (a row with none keeps its slice-0 piece), long rows ascending, are
 //     packed whole into BINS of bin_cap entries (padding
@@ -164,7 +164,7 @@ struct CsrDev {
   int32_t n_slices;         // column slices of the long rows (1, 2, 4 or 8 <= kSlices)
   int64_t n;
   int64_t E;                // elements per workgroup of the element-wise kernels
-  // Replicated-long-row partition (tpl_runtime.cpp, "hybrid"): the SpMV stores each
+  // Replicated-long-row partition (tpl_operator.cpp csr_dev, "hybrid"): the SpMV stores each
   // long row's rank-local partial in ypart[ri] instead of finishing the row, and the
   // norm partials cover elements [0, norm_n) only (replicated entries count once).
   double* ypart;            // n_long partials of this rank (own slice of the all-gather)

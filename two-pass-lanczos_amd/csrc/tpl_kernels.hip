@@ -28,6 +28,7 @@
 // (entries -> gathers); a long-row bin the same two plus an LDS pass, and the
 // slice-7 bins one more (polling the other slices' partials).
 #include "tpl_kcommon.h"
+#include "tpl_launch.h"
 
 namespace tpl {
 

@@ -1,0 +1,51 @@
+// tpl_launch.h — the kernel launchers: declared here once, defined in tpl_kernels.hip,
+// called by the host units. Each enqueues on `s` and returns the launch's status.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "tpl_device.h"
+
+namespace tpl {
+namespace launch {
+hipError_t spmv(const CsrDev& A, const double* x, double* y, hipStream_t s);
+hipError_t p1_init(const CsrDev& A, const DevState& S, const double* b, hipStream_t s);
+// stamp: workgroup 0 records the launch's start there (live timing), or nullptr
+hipError_t p1_spmv(const CsrDev& A, const DevState& S, const double* xsrc, const double* r_cur,
+                   const double* r_prev, double* W, double* Vcol, int j, hipStream_t s,
+                   unsigned long long* stamp = nullptr);
+// elim: one more workgroup eliminates row j - 3 of T_k's LU (one-graph inv)
+hipError_t p1_axpy(const CsrDev& A, const DevState& S, const double* W, const double* r_cur,
+                   double* r_next, int j, int k, int elim, hipStream_t s,
+                   unsigned long long* stamp = nullptr);
+hipError_t p2_tail(int64_t n, const DevState& S, double* x, double* const V[3], hipStream_t s);
+hipError_t permute(int64_t n, int cols, double* out, int64_t ldo, const double* in, int64_t ldi,
+                   const int32_t* idx, hipStream_t s);
+hipError_t ftk_inv(const DevState& S, int kcap, int scale, hipStream_t s);
+hipError_t ftk_exp(const DevState& S, int kcap, int scale, hipStream_t s);
+hipError_t p2_init(int64_t n, const DevState& S, const double* b, double* v1, double* x,
+                   double* Vcol, int dyn, hipStream_t s);
+// nflush: x terms the step applies (tpl::p2_flush: every third step and the last)
+hipError_t p2_spmv(const CsrDev& A, const DevState& S, const double* xsrc, const double* v_cur,
+                   const double* v_prev, double* v_next, double* x, double* Vcol, int j,
+                   int nflush, hipStream_t s);
+// pass-two step records (EpiPass2R) for steps 1 .. k-1; dyn: activity from the device count
+hipError_t p2_coefs(const DevState& S, int k, int dyn, hipStream_t s);
+hipError_t gemv_recon(int64_t n, int steps, const DevState& S, const double* V, double* x,
+                      hipStream_t s);
+int long_epi_blocks(const CsrDev& A);  // workgroups over the long rows (kLongEpiRows each)
+hipError_t long_epi_p1(const CsrDev& A, const DevState& S, const double* yall, int R,
+                       const double* r_cur, const double* r_prev, double* W, double* Vcol,
+                       double* Pa_long, int j, hipStream_t s);
+hipError_t long_epi_p2(const CsrDev& A, const DevState& S, const double* yall, int R,
+                       const double* v_cur, const double* v_prev, double* v_next, double* x,
+                       double* Vcol, int j, int nflush, hipStream_t s);
+hipError_t long_epi_y(const CsrDev& A, const double* yall, int R, double* y, hipStream_t s);
+hipError_t reorth_decide(const DevState& S, const double* Pb1, int G2, int* skip, int* rec,
+                         hipStream_t s);
+hipError_t reorth_dot(int64_t n, int cols, const double* V, const double* r, double* P, int G,
+                      int64_t E, const int* skip, hipStream_t s);
+hipError_t reorth_reduce(int cols, const double* P, int G, double* h, const int* skip, hipStream_t s);
+hipError_t reorth_update(int64_t n, int cols, const double* V, double* r, const double* h,
+                         double* Pnorm, int G, int64_t E, const int* skip, hipStream_t s);
+} // namespace launch
+} // namespace tpl

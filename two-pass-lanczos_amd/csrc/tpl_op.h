@@ -1,0 +1,257 @@
+// tpl_op.h — the handles behind the C ABI (include/tpl.h) and the helpers the host units
+// share. Internal: tpl_operator.cpp (lifetime, buffers, schedule), tpl_dist.cpp (the
+// rank-to-rank transport), tpl_passes.cpp (launch sequences, graph cache), tpl_solvers.cpp
+// (solver entry points) and tpl_profile.cpp (timing, profiling, tuning) include it.
+//
+// Ownership: each handle's destructor releases what the handle owns, and nothing else
+// does — tpl_*_destroy set the device, synchronise and delete, and a create that throws
+// partway releases through the same destructor.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "tpl_device.h"
+#include "tpl_internal.h"
+#include "tpl_launch.h"
+#include "tpl_layout.h"
+#include "tpl_partition.h"
+
+typedef struct ncclComm* ncclComm_t;  // rccl/rccl.h's own typedef: only tpl_dist.cpp includes it
+
+namespace tpl {
+
+#define HIPCHK(expr)                                                                        \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      ::tpl::fail(e_ == hipErrorOutOfMemory ? TPL_ERR_OUT_OF_MEMORY : TPL_ERR_DEVICE,       \
+                  std::string(#expr) + ": " + hipGetErrorString(e_));                       \
+  } while (0)
+
+template <class F>
+tpl_status guarded(F&& f) {
+  try {
+    f();
+    set_last_error("");
+    return TPL_OK;
+  } catch (const Error& e) {
+    // a failed HIP call leaves its status as the runtime's "last error", which the next
+    // launch's hipGetLastError() check would report as its own: clear it here
+    if (e.code == TPL_ERR_DEVICE || e.code == TPL_ERR_OUT_OF_MEMORY) (void)hipGetLastError();
+    set_last_error(e.code, e.msg, e.det);
+    return e.code;
+  } catch (const std::bad_alloc&) {
+    set_last_error(TPL_ERR_OUT_OF_MEMORY, "host allocation failed", {});
+    return TPL_ERR_OUT_OF_MEMORY;
+  } catch (const std::exception& e) {
+    set_last_error(TPL_ERR_INVALID_ARGUMENT, e.what(), {});
+    return TPL_ERR_INVALID_ARGUMENT;
+  }
+}
+
+// The device buffers of a Layout (and of its row order): rebuild_schedule replaces the set.
+struct LayoutBufs {
+  void *d_scol = nullptr, *d_sval = nullptr, *d_bcol = nullptr, *d_bval = nullptr;
+  int32_t *d_srows = nullptr, *d_scbase = nullptr, *d_cbase = nullptr, *d_cwidth = nullptr;
+  int32_t *d_bcbase = nullptr, *d_bhdr = nullptr;
+  BinSeg* d_bseg = nullptr;
+  double* d_P = nullptr;
+  unsigned int* d_Pcnt = nullptr;
+  int32_t *d_perm = nullptr, *d_iperm = nullptr;  // locality order (empty perm: nullptr)
+  double* d_stage = nullptr;        // one host-order vector (host uploads / downloads)
+};
+
+// The solver state of an operator, sized for kcap steps: ensure_state replaces the set.
+struct SolverState {
+  size_t kcap = 0;
+  void* d_state = nullptr;  // flags | norms | alphas | betas | y | Pa | Pb | p2c | lu
+  void* h_state = nullptr;  // pinned mirror of flags | norms | alphas | betas
+  DevState S{};
+  double* d_Pr = nullptr;   // reorthogonalisation partials (G * kcap)
+};
+
+struct GraphExecDelete {
+  void operator()(hipGraphExec_t g) const { hipGraphExecDestroy(g); }
+};
+using GraphExec = std::unique_ptr<hipGraphExec, GraphExecDelete>;
+
+} // namespace tpl
+
+// ---------------------------------------------------------------- objects
+struct tpl_ctx_s {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  tpl_ctx_s() = default;
+  tpl_ctx_s(const tpl_ctx_s&) = delete;
+  ~tpl_ctx_s() {
+    if (stream) hipStreamDestroy(stream);
+  }
+};
+
+// A rank of a row-partitioned operator (tpl_dist_create*): its GPU and stream, and the
+// transport of the per-step exchanges — RCCL over xGMI, or (tests) a host callback.
+struct tpl_dist_s {
+  tpl_ctx_s ctx;
+  int rank = 0, nranks = 1;
+  ncclComm_t comm = nullptr;
+  tpl_allgather_fn host_fn = nullptr;
+  void* host_user = nullptr;
+  ~tpl_dist_s();  // the communicator, then (ctx) the stream; a plan's has neither
+};
+
+struct tpl_op_s {
+  int device = 0;
+  hipStream_t stream = nullptr;     // the ctx's or the dist's: not owned
+  // this operator's rows, their CSR (h_rowptr / h_col / h_val keep the caller's order)
+  // and its place in the partition; single GPU: dist == nullptr, n_glob == n
+  tpl::RankPlan part;
+  tpl_dist_s* dist = nullptr;
+  bool eager = false;               // launch without graphs (host transport / no capture)
+  double* d_yall = nullptr;         // nranks x y_ld1 (pass one: long-row partials + the
+                                    // rank's short-chunk alpha partials, all-gathered
+                                    // together); pass two: nranks x (n_long + 1)
+  int32_t y_ld1 = 0;                // n_long + the most chunks of any rank
+  int32_t pb_ld = 0;                // > 0: every rank's norm partials all-gathered (CsrDev::pb_ld)
+  double* d_pball = nullptr;        // [nranks x pb_ld] gathered norm partials (pb_ld > 0)
+  int32_t* d_nch = nullptr;
+  int32_t* d_halo_send = nullptr;
+  tpl::SchedParams sp;
+  tpl::Layout lay;
+  tpl::LayoutBufs bufs;
+  // vectors: b, R0..R2, W, x, V2_0..V2_2, tmp (n each, padded)
+  double* d_vecs = nullptr;
+  int64_t ld = 0;
+  double *b = nullptr, *R[3] = {nullptr, nullptr, nullptr}, *W = nullptr, *x = nullptr,
+         *V2[3] = {nullptr, nullptr, nullptr}, *tmp = nullptr;
+  // gather sources of the SpMV: the same buffers on one GPU; with a partition, the
+  // all-gathered vectors (nranks x ld) whose rank-th slice the local pointers view
+  double *bG = nullptr, *RG[3] = {nullptr, nullptr, nullptr}, *V2G[3] = {nullptr, nullptr, nullptr},
+         *tmpG = nullptr;
+  double* d_rsum = nullptr;         // [nranks alpha totals][nranks norm totals] (partition)
+  tpl::SolverState st;
+  double* d_V = nullptr;    // standard-variant basis (n x vcols, ld = n); nullptr: vcols == 0
+  size_t vcols = 0;
+  std::map<std::pair<int, size_t>, tpl::GraphExec> graphs;
+  // device allocations of this operator (pointer -> bytes): tpl_op_device_bytes
+  std::map<const void*, size_t> allocs;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // live timing (tpl_op_enable_timing): events recorded inside the captured passes
+  bool timing = false;
+  int device_ftk = 2;               // built-in inv on the device (one graph): 0 off, 1 on, 2 auto
+  bool last_one_graph = false;      // the last tpl_lanczos_two_pass ran as one device graph
+  int64_t reorth_second = 0;        // second Gram-Schmidt passes of the last reorth solve
+  // locality order (single GPU, tpl_op_set_reorder): the device works on P A P^T; vectors
+  // cross the boundary through a gather (internal i <- caller's perm[i], back via iperm).
+  int reorder = 2;                  // 0 off, 1 on, 2 auto (n <= kReorderAutoMaxRows)
+  std::vector<int32_t> perm, iperm;
+  double* d_Vext = nullptr;         // the callback's V_k view in the caller's order
+  size_t vext_cols = 0;             // (nullptr: vext_cols == 0)
+  hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
+  int64_t p2_launches = 0;
+  // live timing of pass one's kernels: start stamps of the last timed solve's sampled
+  // launches (2 kStampSteps + 1), tpl_op_step_samples
+  unsigned long long* d_stamps = nullptr;
+  int32_t p1_samples = 0;
+  // tpl_plan_create: the host half of an operator only (rows, order, layout), for the
+  // oracle's reduction order without a GPU; every device entry point refuses it
+  bool plan_only = false;
+  std::unique_ptr<tpl_dist_s> plan_dist;  // a plan's rank and rank count (no transport)
+  // Graphs, every entry of allocs, the pinned mirror, the events. A host-only plan holds
+  // none of them and its destructor makes no HIP call.
+  ~tpl_op_s();
+};
+
+namespace tpl {
+
+// ---- operator (tpl_operator.cpp) ---------------------------------------------------
+int long_epi_blocks(const tpl_op_s* op);
+CsrDev csr_dev(const tpl_op_s* op, bool pass1 = false);
+inline void drop_graphs(tpl_op_s* op) { op->graphs.clear(); }
+
+// Device memory of an operator, accounted per allocation (tpl_op_device_bytes): the one
+// allocation path. Test hook: with TPL_TEST_ALLOC_CAP=<bytes> set (read on every call), a
+// request that would take the accounted bytes above the cap is refused on the host as
+// hipErrorOutOfMemory is reported, and never reaches the runtime.
+void dev_alloc_bytes(tpl_op_s* op, void** p, size_t bytes);
+template <class T>
+void dev_alloc(tpl_op_s* op, T** p, size_t bytes) {
+  dev_alloc_bytes(op, reinterpret_cast<void**>(p), bytes);
+}
+template <class T>
+void dev_free(tpl_op_s* op, T*& p) {
+  if (!p) return;
+  op->allocs.erase(p);
+  hipFree(p);
+  p = nullptr;
+}
+uint64_t device_bytes(const tpl_op_s* op);
+
+void rebuild_schedule(tpl_op_s* op, const SchedParams& cand, int reorder);
+void ensure_state(tpl_op_s* op, size_t k, bool reorth = false);
+void ensure_basis(tpl_op_s* op, size_t cols);
+double* ensure_view(tpl_op_s* op, size_t cols);
+// Per-step second-pass records of the selective re-orthogonalisation (slot j - 1: step j).
+int* reorth_records(const tpl_op_s* op);
+void set_device(const tpl_op_s* op);
+inline void sync_checked(tpl_op_s* op) { HIPCHK(hipStreamSynchronize(op->stream)); }
+void check_b(const tpl_op_s* op, const double* b, int64_t b_len);
+void upload_vec(tpl_op_s* op, double* dst, const double* src, int mem);
+void download_vec(tpl_op_s* op, double* dst, const double* src, int64_t cols, int mem);
+void set_stride(tpl_op_s* op);
+std::unique_ptr<tpl_op_s> make_op(tpl_ctx_s* ctx, tpl_dist_s* dist, RankPlan&& part);
+void init_op(tpl_op_s* op);
+
+// ---- dist (tpl_dist.cpp): the exchanges of a row-partitioned operator ---------------
+void dist_allgather(tpl_op_s* op, double* base, size_t count);
+void halo_pack(tpl_op_s* op, double* G);
+void gather_vec(tpl_op_s* op, double* G);
+void enqueue_p1_exchange_a(tpl_op_s* op, const CsrDev& A);
+void enqueue_p1_exchange_norm(tpl_op_s* op, const CsrDev& A, double* G);
+void enqueue_p2_exchange(tpl_op_s* op, int j);
+
+// ---- passes (tpl_passes.cpp) -------------------------------------------------------
+// Live timing of pass one's kernels (tpl_op_step_samples): in a timed solve, workgroup 0
+// of the k_p1_spmv and k_p1_axpy launches of kStampSteps consecutive middle steps (and of
+// the next step's k_p1_spmv) records its start on the 100 MHz real-time clock; a kernel's
+// launch time is the start-to-start interval, boundary included (as pass two's figure).
+constexpr int kStampSteps = 8;
+// Which built-in f(T_k) a solve evaluates on the device (kDevHost: none, f runs on the host).
+enum DevF { kDevHost = -1, kDevInv = 0, kDevExp = 1 };
+
+struct HostDecomp {
+  int32_t flags[kFlagBytes / 4];
+  double b_norm;
+  const double* alphas;
+  const double* betas;
+  size_t steps;
+};
+
+bool use_graphs();
+// `enqueue` captured on the operator's stream into an executable graph. nullptr: a
+// partitioned operator's transport refused capture (or the graph could not be
+// instantiated) and the operator launches eagerly from now on (op->eager); any other
+// failure throws. No graph object outlives a failure.
+GraphExec capture_graph(tpl_op_s* op, const std::function<void()>& enqueue);
+void enqueue_reorth(tpl_op_s* op, int j, int mode);
+void enqueue_p1_prologue(tpl_op_s* op);
+void enqueue_p1_step(tpl_op_s* op, int j, int k, double* Vcol, bool elim = false,
+                     unsigned long long* st1 = nullptr, unsigned long long* st2 = nullptr);
+void launch_p2_step(tpl_op_s* op, const CsrDev& A, int j, int t, int nflush, double* Vcol);
+void enqueue_pass2(tpl_op_s* op, size_t steps, double* Vout);
+void enqueue_ftk_only(tpl_op_s* op, size_t k, int f, int scale);
+void run_pass_one(tpl_op_s* op, const double* b, size_t k, int mem, bool storeV, int reorth,
+                  bool elim = false);
+void run_pass2(tpl_op_s* op, size_t steps);
+void run_two_pass_dev(tpl_op_s* op, size_t k, int f);
+HostDecomp fetch_decomp(tpl_op_s* op);
+
+} // namespace tpl

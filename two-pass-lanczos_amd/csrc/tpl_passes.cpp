@@ -1,0 +1,312 @@
+// tpl_passes.cpp — the per-step launch sequences of the device-resident Lanczos passes
+// and the graph cache that replays them.
+//
+// The Lanczos loops of the reference (src/algorithms/lanczos.rs:86-128,
+// src/algorithms/lanczos_two_pass.rs:84-102 and :266-309) run entirely on the GPU:
+// the per-step launches are captured once per (variant, k) into a hipGraph and
+// replayed, alpha/beta never leave HBM during a pass, and breakdown is handled
+// on the device (a stop flag turns the remaining launches into no-ops). The only
+// host round trip of a solve is the f(T_k) call between the passes, exactly
+// where the reference calls its closure (src/solvers.rs:71-75, :155-156).
+#include "tpl_op.h"
+
+namespace tpl {
+
+namespace {
+enum GraphKind {
+  kGPass1 = 0,        // pass one: + the kP1* properties of the variant (kinds 0 .. 7)
+  kGPass2 = 8, kGPass2Steps,
+  kGTwoPassDev,       // one-graph solve: pass one, device f(T_k), pass two
+  kGDevFtk,           // (timed variant) device f(T_k) + pass-two prologue
+  kGPass2Dyn,         // (timed variant) the k - 1 step launches of a one-graph solve
+};
+// What tells one pass-one sequence (and its graph) from another, beside k: the basis is
+// stored (the standard pass), T_k's LU is eliminated as it goes (a device inv follows:
+// k_ftk_inv), kStampSteps steps carry start stamps (timed variant).
+enum P1Props { kP1Basis = 1, kP1Elim = 2, kP1Stamped = 4 };
+
+// r_j buffer of pass one: r_1 = b, then R[j % 3] (local view, and gather source).
+inline double* r_of(const tpl_op_s* op, int j) { return j == 1 ? op->b : op->R[j % 3]; }
+inline double* rG_of(const tpl_op_s* op, int j) { return j == 1 ? op->bG : op->RG[j % 3]; }
+
+// Pass two's three basis buffers at position t of their rotation (a sweep's step j sits
+// at t = j): the gather source and local view of v_t, v_{t-1}, and v_{t+1}'s place.
+struct P2Rot {
+  double *G, *cur, *prev, *next;
+};
+inline P2Rot p2_rot(const tpl_op_s* op, int t) {
+  return {op->V2G[t % 3], op->V2[t % 3], op->V2[(t + 2) % 3], op->V2[(t + 1) % 3]};
+}
+} // namespace
+
+bool use_graphs() {
+  const char* e = std::getenv("TPL_NO_GRAPH");
+  return !(e && e[0] == '1');
+}
+
+// ---- reorthogonalisation (extension, not in the reference): classical Gram-Schmidt of
+// r_{j+1} against the stored columns V[:, 0..j) before beta_j. mode 1 (CGS2): two
+// passes, always. mode 2 (selective, Kahan–Parlett "twice is enough"): the second pass
+// runs only when the first removed more than half of ||r||^2 (k_reorth_decide; its
+// kernels see the device flag and return at once otherwise).
+void enqueue_reorth(tpl_op_s* op, int j, int mode) {
+  if (op->dist) fail(TPL_ERR_UNSUPPORTED, "re-orthogonalisation of a partitioned operator");
+  const int cols = j; // v_1 .. v_j are stored in V[:, 0..j)
+  const int G2 = op->lay.G2;
+  const int64_t E = op->lay.E;
+  double* P = op->st.d_Pr;                             // cols x G2 partials
+  double* h = op->st.d_Pr + (size_t)G2 * op->st.kcap;  // cols coefficients
+  double* Pb1 = h + op->st.kcap;                       // ||r'||^2 partials (selective)
+  int* skip = reinterpret_cast<int*>(Pb1 + G2);
+  int* rec = reorth_records(op) + (j - 1);
+  double* r = op->R[(j + 1) % 3];
+  for (int pass = 0; pass < 2; ++pass) {
+    const int* sk = (mode == 2 && pass == 1) ? skip : nullptr;
+    HIPCHK(launch::reorth_dot(op->part.n, cols, op->d_V, r, P, G2, E, sk, op->stream));
+    HIPCHK(launch::reorth_reduce(cols, P, G2, h, sk, op->stream));
+    // the last update rewrites the ||r||^2 partials that k_p1_spmv(j+1) reduces; in the
+    // selective mode the first one writes its own partials for the decision
+    double* pn = pass == 1 ? op->st.S.Pb : (mode == 2 ? Pb1 : nullptr);
+    HIPCHK(launch::reorth_update(op->part.n, cols, op->d_V, r, h, pn, G2, E, sk, op->stream));
+    if (mode == 2 && pass == 0)
+      HIPCHK(launch::reorth_decide(op->st.S, Pb1, G2, skip, rec, op->stream));
+  }
+}
+
+// Pass one prologue: ||b||^2 partials; with a partition, b and the per-rank
+// totals are all-gathered (step 1 gathers from b).
+void enqueue_p1_prologue(tpl_op_s* op) {
+  const CsrDev A = csr_dev(op);
+  HIPCHK(launch::p1_init(A, op->st.S, op->b, op->stream));
+  if (op->dist) enqueue_p1_exchange_norm(op, A, op->bG);
+}
+
+// Pass one, step j (k = requested steps). elim: also eliminate row j - 3 of T_k's LU
+// (the one-graph inv, k_p1_axpy).
+// st1 / st2: start stamps of the step's k_p1_spmv / k_p1_axpy launch (live timing), or nullptr.
+void enqueue_p1_step(tpl_op_s* op, int j, int k, double* Vcol, bool elim, unsigned long long* st1,
+                     unsigned long long* st2) {
+  const CsrDev A = csr_dev(op, true);
+  HIPCHK(launch::p1_spmv(A, op->st.S, rG_of(op, j), r_of(op, j), j >= 2 ? r_of(op, j - 1) : nullptr,
+                         op->W, Vcol, j, op->stream, st1));
+  if (op->dist) enqueue_p1_exchange_a(op, A);
+  if (op->part.hybrid)
+    HIPCHK(launch::long_epi_p1(A, op->st.S, op->d_yall, op->dist->nranks, r_of(op, j),
+                               j >= 2 ? r_of(op, j - 1) : nullptr, op->W, Vcol,
+                               op->d_rsum + op->dist->nranks, j, op->stream));
+  HIPCHK(launch::p1_axpy(A, op->st.S, op->W, r_of(op, j), op->R[(j + 1) % 3], j, k,
+                         elim ? 1 : 0, op->stream, st2));
+  if (op->dist && j < k) enqueue_p1_exchange_norm(op, A, op->RG[(j + 1) % 3]);
+}
+
+// First stamped step of a k-step pass one (steps js .. js + kStampSteps - 1, and the
+// k_p1_spmv of the step after), or 0: the pass is too short to sample.
+static int stamp_first(size_t k) {
+  return k >= (size_t)kStampSteps + 3 ? (int)(k - kStampSteps) / 2 + 1 : 0;
+}
+
+static void enqueue_pass1(tpl_op_s* op, size_t k, int props, int reorth = 0) {
+  enqueue_p1_prologue(op);
+  const int js = props & kP1Stamped ? stamp_first(k) : 0;
+  for (int j = 1; j <= (int)k; ++j) {
+    double* Vcol = props & kP1Basis ? op->d_V + (size_t)(j - 1) * op->part.n : nullptr;
+    const int i = j - js;  // stamp slots: spmv of step js + i at 2i, its axpy at 2i + 1
+    unsigned long long* st1 = js && i >= 0 && i <= kStampSteps ? op->d_stamps + 2 * i : nullptr;
+    unsigned long long* st2 = js && i >= 0 && i < kStampSteps ? op->d_stamps + 2 * i + 1 : nullptr;
+    enqueue_p1_step(op, j, (int)k, Vcol, (props & kP1Elim) != 0, st1, st2);
+    if (reorth && j < (int)k) enqueue_reorth(op, j, reorth);
+  }
+}
+
+static void enqueue_pass2_init(tpl_op_s* op, size_t steps, double* Vout) {
+  HIPCHK(launch::p2_init(op->part.n, op->st.S, op->b, op->V2[1], op->x, Vout, 0, op->stream));
+  HIPCHK(launch::p2_coefs(op->st.S, (int)steps, 0, op->stream));
+  if (op->dist && !op->part.hybrid) {
+    halo_pack(op, op->V2G[1]);
+    gather_vec(op, op->V2G[1]);
+  }
+}
+
+// The pass-two step launch: step record j, the buffers at position t of their rotation
+// (a sweep: t = j; the profiler re-runs one step's record as the buffers turn).
+void launch_p2_step(tpl_op_s* op, const CsrDev& A, int j, int t, int nflush, double* Vcol) {
+  const P2Rot v = p2_rot(op, t);
+  HIPCHK(launch::p2_spmv(A, op->st.S, v.G, v.cur, j >= 2 ? v.prev : nullptr, v.next, op->x, Vcol,
+                         j, nflush, op->stream));
+}
+
+static void enqueue_pass2_steps(tpl_op_s* op, size_t steps, double* Vout) {
+  const CsrDev A = csr_dev(op);
+  for (int j = 1; j < (int)steps; ++j) {
+    double* Vcol = Vout ? Vout + (size_t)j * op->part.n : nullptr;
+    const int nflush = p2_flush(j, (int)steps - 1);
+    launch_p2_step(op, A, j, j, nflush, Vcol);
+    if (op->part.hybrid) {
+      const P2Rot v = p2_rot(op, j);
+      enqueue_p2_exchange(op, j);
+      HIPCHK(launch::long_epi_p2(A, op->st.S, op->d_yall, op->dist->nranks, v.cur,
+                                 j >= 2 ? v.prev : nullptr, v.next, op->x, Vcol, j, nflush,
+                                 op->stream));
+    } else if (op->dist && j + 1 < (int)steps) {
+      enqueue_p2_exchange(op, j);
+    }
+  }
+}
+void enqueue_pass2(tpl_op_s* op, size_t steps, double* Vout) {
+  enqueue_pass2_init(op, steps, Vout);
+  enqueue_pass2_steps(op, steps, Vout);
+}
+
+// ---- one-graph two-pass solve (built-in f = inv, single GPU): steps_taken stays on the
+// device. Pass one as usual; k_ftk_inv forms y = ||b|| T^{-1} e_1 from the device alpha /
+// beta (bitwise the host solver's result); pass two is the k - 1 step launches, those at
+// or past steps_taken doing nothing, with x flushed at multiples of 3 only and the
+// pending terms of the last step added by k_p2_tail (the same sums as the host schedule).
+// y = f(T_k) e_1 from the device alpha / beta, times ||b|| (scale: the two-pass y_k) or not
+// (the one-pass y').
+void enqueue_ftk_only(tpl_op_s* op, size_t k, int f, int scale) {
+  if (f == kDevExp)
+    HIPCHK(launch::ftk_exp(op->st.S, (int)k, scale, op->stream));
+  else
+    HIPCHK(launch::ftk_inv(op->st.S, (int)k, scale, op->stream));
+}
+static void enqueue_ftk_dev(tpl_op_s* op, size_t k, int f) {
+  enqueue_ftk_only(op, k, f, 1);
+  HIPCHK(launch::p2_init(op->part.n, op->st.S, op->b, op->V2[1], op->x, nullptr, 1, op->stream));
+  HIPCHK(launch::p2_coefs(op->st.S, (int)k, 1, op->stream));
+}
+static void enqueue_pass2_dyn_steps(tpl_op_s* op, size_t k) {
+  const CsrDev A = csr_dev(op);
+  for (int j = 1; j < (int)k; ++j) launch_p2_step(op, A, j, j, j % 3 == 0 ? 3 : 0, nullptr);
+}
+static void enqueue_pass2_tail(tpl_op_s* op) {
+  HIPCHK(launch::p2_tail(op->part.n, op->st.S, op->x, op->V2, op->stream));
+}
+
+GraphExec capture_graph(tpl_op_s* op, const std::function<void()>& enqueue) {
+  auto go_eager = [&]() -> GraphExec {
+    op->eager = true;  // the transport refused capture: launch eagerly from now on
+    hipGetLastError();
+    return nullptr;
+  };
+  HIPCHK(hipStreamBeginCapture(op->stream, hipStreamCaptureModeThreadLocal));
+  hipGraph_t g = nullptr;
+  try {
+    enqueue();
+  } catch (...) {
+    hipStreamEndCapture(op->stream, &g);
+    if (g) hipGraphDestroy(g);
+    if (!op->dist) throw;
+    return go_eager();
+  }
+  hipError_t e = hipStreamEndCapture(op->stream, &g);
+  hipGraphExec_t ge = nullptr;
+  if (e == hipSuccess) e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+  if (g) hipGraphDestroy(g);
+  if (e != hipSuccess && op->dist) return go_eager();
+  HIPCHK(e);
+  return GraphExec(ge);
+}
+
+template <class Enq>
+static void run_graph(tpl_op_s* op, int kind, size_t key, Enq&& enqueue) {
+  if (!use_graphs() || op->eager) {
+    enqueue();
+    return;
+  }
+  auto it = op->graphs.find({kind, key});
+  if (it == op->graphs.end()) {
+    GraphExec ge = capture_graph(op, [&] { enqueue(); });
+    if (!ge) {
+      enqueue();
+      return;
+    }
+    it = op->graphs.emplace(std::make_pair(kind, key), std::move(ge)).first;
+  }
+  HIPCHK(hipGraphLaunch(it->second.get(), op->stream));
+}
+
+static void run_pass1_graph(tpl_op_s* op, size_t k, int props) {
+  run_graph(op, kGPass1 + props, k, [&] { enqueue_pass1(op, k, props); });
+}
+
+// Pass two without a basis. With live timing on, the prologue is launched on its own
+// and events bracket the graph of the steps - 1 step launches (tpl_op_pass_timing).
+void run_pass2(tpl_op_s* op, size_t steps) {
+  if (!op->timing) {
+    run_graph(op, kGPass2, steps, [&] { enqueue_pass2(op, steps, nullptr); });
+    return;
+  }
+  enqueue_pass2_init(op, steps, nullptr);
+  HIPCHK(hipEventRecord(op->tev[2], op->stream));
+  run_graph(op, kGPass2Steps, steps, [&] { enqueue_pass2_steps(op, steps, nullptr); });
+  HIPCHK(hipEventRecord(op->tev[3], op->stream));
+  op->p2_launches = (int64_t)steps - 1;
+}
+
+// Copy flags | norms[0] | alphas | betas back (one D2H), synchronise.
+HostDecomp fetch_decomp(tpl_op_s* op) {
+  const size_t kc = op->st.kcap;
+  char* h = (char*)op->st.h_state;
+  const size_t bytes = kFlagBytes + ((kc + 1) + 2 * kc) * sizeof(double);
+  HIPCHK(hipMemcpyAsync(h, op->st.d_state, bytes, hipMemcpyDeviceToHost, op->stream));
+  sync_checked(op);
+  HostDecomp d;
+  std::memcpy(d.flags, h, kFlagBytes);
+  const double* norms = (const double*)(h + kFlagBytes);
+  d.b_norm = norms[0];
+  d.alphas = norms + (kc + 1);
+  d.betas = d.alphas + kc;
+  d.steps = (size_t)d.flags[2];
+  return d;
+}
+
+// The whole two-pass solve as one graph (or, with live timing on, as several graphs with
+// the events between them); no host round trip between the passes.
+void run_two_pass_dev(tpl_op_s* op, size_t k, int f) {
+  const size_t key = 2 * k + (size_t)f;  // one graph per (k, f)
+  const int elim = f == kDevInv ? kP1Elim : 0;  // T_k's LU eliminated during pass one
+  if (!op->timing) {
+    op->p1_samples = 0;  // the untimed graph records no launch stamps
+    run_graph(op, kGTwoPassDev, key, [&] {
+      enqueue_pass1(op, k, elim);
+      enqueue_ftk_dev(op, k, f);
+      enqueue_pass2_dyn_steps(op, k);
+      enqueue_pass2_tail(op);
+    });
+    return;
+  }
+  HIPCHK(hipEventRecord(op->tev[0], op->stream));
+  const bool stamped = !op->dist && stamp_first(k) > 0;
+  if (stamped && !op->d_stamps) {
+    dev_alloc(op, &op->d_stamps, 32 * sizeof(unsigned long long));
+    HIPCHK(hipMemset(op->d_stamps, 0, 32 * sizeof(unsigned long long)));
+  }
+  run_pass1_graph(op, k, elim | (stamped ? kP1Stamped : 0));
+  op->p1_samples = stamped ? kStampSteps : 0;
+  HIPCHK(hipEventRecord(op->tev[1], op->stream));
+  run_graph(op, kGDevFtk, key, [&] { enqueue_ftk_dev(op, k, f); });
+  HIPCHK(hipEventRecord(op->tev[2], op->stream));
+  run_graph(op, kGPass2Dyn, k, [&] { enqueue_pass2_dyn_steps(op, k); });
+  HIPCHK(hipEventRecord(op->tev[3], op->stream));
+  enqueue_pass2_tail(op);
+  op->p2_launches = (int64_t)k - 1;
+}
+
+// elim: eliminate T_k's LU during the pass (a device inv follows: k_ftk_inv)
+void run_pass_one(tpl_op_s* op, const double* b, size_t k, int mem, bool storeV, int reorth,
+                  bool elim) {
+  ensure_state(op, k, reorth);
+  if (storeV) ensure_basis(op, k);
+  upload_vec(op, op->b, b, mem);
+  op->p1_samples = 0;  // no pass run here records launch stamps (tpl_op_step_samples)
+  if (reorth) {
+    enqueue_pass1(op, k, kP1Basis, reorth); // eager: reorth launch counts vary with j
+  } else {
+    if (op->timing) HIPCHK(hipEventRecord(op->tev[0], op->stream));
+    run_pass1_graph(op, k, (storeV ? kP1Basis : 0) | (elim ? kP1Elim : 0));
+    if (op->timing) HIPCHK(hipEventRecord(op->tev[1], op->stream));
+  }
+}
+
+} // namespace tpl

@@ -1,0 +1,393 @@
+// tpl_solvers.cpp — the solver entry points of the C ABI (include/tpl.h): the SpMV, the
+// passes on their own, and the one- and two-pass solves with their f(T_k) on the host or
+// on the device.
+#include "tpl_op.h"
+
+using namespace tpl;
+
+namespace {
+// Callback polling (tpl_lanczos_standard with a step callback): largest batch of steps
+// run ahead of the host callback.
+constexpr int kCbBatchMax = 32;
+// One-graph solves keep the device f(T_k)'s working rows in LDS (k_ftk_inv: 11 k doubles,
+// 120 KB at this k; gfx950 has 160 KiB of LDS per workgroup).
+constexpr size_t kDevFtkMaxK = 1365;
+// Auto mode: the device inv up to k = 500, the largest k at which it was measured no
+// slower than the host round trip it replaces. Its elimination runs during pass one
+// (k_p1_axpy's extra workgroup) and its back substitution with Markstein divisions (round
+// 4, same box, profiles/r04_ftk_timing.txt: 0.574 vs 0.583 ms at 5k arcs k = 50, 2.390 vs
+// 2.412 at 50k k = 200, 9.312 vs 9.315 ms at the 500k headline k = 500); past that the
+// serial back substitution grows longer than the round trip (round 5, same box,
+// profiles/r05_ftk_timing.txt: 10.36 vs 10.24 ms at 5k arcs k = 1000, 14.16 vs 13.84 at
+// k = 1365; 11.18 vs 10.99 and 15.62 vs 15.05 ms at 50k arcs). Mode 1 still takes the
+// device inv up to kDevFtkMaxK.
+constexpr size_t kDevFtkAutoK = 500;
+// The device exp (k_ftk_exp, a Chebyshev expansion: parallel over the rows of T_k) keeps
+// 4 k + 4 doubles of dynamic LDS plus 8.2 KB of static arrays: 65.8 KB at this k, which
+// gfx950's 160 KiB of LDS per workgroup holds (a 64 KiB part would need k <= 1790).
+constexpr size_t kDevExpMaxK = 1800;
+
+void check_k(size_t k) {
+  // The reference panics at k = 0 (Vec::with_capacity(k - 1) underflow,
+  // src/algorithms/lanczos.rs:75); the C ABI reports it instead.
+  if (k == 0) fail_input("The number of iterations `k` must be at least 1.");
+  if (k > (size_t)INT32_MAX / 2) fail(TPL_ERR_INVALID_ARGUMENT, "k too large");
+}
+
+void call_ftk(tpl_ftk_fn f, void* user, const HostDecomp& d, std::vector<double>& y) {
+  if (!f) fail(TPL_ERR_INVALID_ARGUMENT, "f_tk_solver is NULL");
+  y.assign(d.steps, 0.0);
+  size_t ylen = d.steps;
+  char err[1024];
+  err[0] = '\0';
+  const int rc = f(d.alphas, d.steps, d.betas, d.steps > 0 ? d.steps - 1 : 0, y.data(), d.steps,
+                   &ylen, err, sizeof(err), user);
+  err[sizeof(err) - 1] = '\0';
+  if (rc != 0) fail_solver(err);
+  if (ylen != d.steps)
+    fail_param_mismatch("y_k_prime", d.steps, ylen);
+}
+
+void zero_out(tpl_op_s* op, double* x_out, int mem) {
+  if (op->part.n == 0) return;
+  if (mem == TPL_MEM_DEVICE) {
+    HIPCHK(hipMemsetAsync(x_out, 0, op->part.n * sizeof(double), op->stream));
+    sync_checked(op);
+  } else {
+    std::memset(x_out, 0, op->part.n * sizeof(double));
+  }
+}
+
+// What a pass's flags decide before any f(T_k): a zero b is an error, and a pass that
+// took no step leaves the zero result (true: x_out holds it).
+bool zero_result(tpl_op_s* op, const int32_t* flags, double* x_out, int mem) {
+  if (flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+  if (flags[2] != 0) return false;
+  zero_out(op, x_out, mem);
+  return true;
+}
+
+// The host half of a solve, between the passes: the zero cases (zero_result), then
+// y' = f(T_k) e_1 by the caller's solver (src/solvers.rs:71-85, :155-165), times ||b|| for
+// the two-pass y_k (scale, :169), into the device state. Returns the steps taken; 0: the
+// solve is over and x_out holds its zero result (:64-66, :150-152).
+size_t host_ftk(tpl_op_s* op, const HostDecomp& d, tpl_ftk_fn f, void* f_user, bool scale,
+                double* x_out, int mem) {
+  if (zero_result(op, d.flags, x_out, mem)) return 0;
+  std::vector<double> y;
+  call_ftk(f, f_user, d, y);
+  if (scale)
+    for (auto& v : y) v = v * d.b_norm;
+  HIPCHK(hipMemcpyAsync(op->st.S.y, y.data(), d.steps * sizeof(double), hipMemcpyHostToDevice,
+                        op->stream));
+  return d.steps;
+}
+
+// A decomposition out to the caller's arrays (a zero b is an error).
+void write_decomp(const HostDecomp& d, double* alphas, double* betas, size_t* steps,
+                  double* b_norm) {
+  if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+  std::memcpy(alphas, d.alphas, d.steps * sizeof(double));
+  if (d.steps > 1) std::memcpy(betas, d.betas, (d.steps - 1) * sizeof(double));
+  *steps = d.steps;
+  *b_norm = d.b_norm;
+}
+
+// Where a k-step solve evaluates f(T_k): on the device for the built-in inv / exp of an
+// operator that is not partitioned, up to the mode's k (tpl_op_set_device_ftk).
+DevF device_f(const tpl_op_s* op, tpl_ftk_fn f, size_t k) {
+  const bool is_inv = f == &tpl_ftk_inv, is_exp = f == &tpl_ftk_exp;
+  const size_t kmax = !op->device_ftk ? 0
+                      : is_inv ? (op->device_ftk == 1 ? kDevFtkMaxK : kDevFtkAutoK)
+                      : is_exp ? kDevExpMaxK : 0;
+  if ((!is_inv && !is_exp) || op->dist || k > kmax) return kDevHost;
+  return is_exp ? kDevExp : kDevInv;
+}
+
+} // namespace
+
+extern "C" {
+
+tpl_status tpl_op_apply(tpl_op_t op, const double* x, double* y, int mem) {
+  return guarded([&] {
+    if (!op || ((!x || !y) && op->part.n > 0)) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    set_device(op);
+    if (op->part.n == 0) return;
+    upload_vec(op, op->tmp, x, mem);
+    if (op->dist && !op->part.hybrid) {
+      halo_pack(op, op->tmpG);
+      gather_vec(op, op->tmpG);
+    }
+    const CsrDev A = csr_dev(op);
+    HIPCHK(launch::spmv(A, op->tmpG, op->W, op->stream));
+    if (op->part.hybrid && A.n_long > 0) {
+      dist_allgather(op, op->d_yall, (size_t)A.y_ld);
+      HIPCHK(launch::long_epi_y(A, op->d_yall, op->dist->nranks, op->W, op->stream));
+    }
+    download_vec(op, y, op->W, 1, mem);
+    sync_checked(op);
+  });
+}
+
+tpl_status tpl_lanczos_pass_one(tpl_op_t op, const double* b, int64_t b_len, size_t k,
+                                double* alphas, double* betas, size_t* steps, double* b_norm,
+                                int mem) {
+  return guarded([&] {
+    if (!op || !alphas || !betas || !steps || !b_norm)
+      fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    set_device(op);
+    check_b(op, b, b_len);
+    check_k(k);
+    run_pass_one(op, b, k, mem, false, false);
+    write_decomp(fetch_decomp(op), alphas, betas, steps, b_norm);
+  });
+}
+
+tpl_status tpl_lanczos_standard(tpl_op_t op, const double* b, int64_t b_len, size_t k,
+                                double* alphas, double* betas, size_t* steps, double* b_norm,
+                                double* v_out, int mem, int reorth, tpl_step_cb cb,
+                                void* cb_user) {
+  return guarded([&] {
+    if (!op || !alphas || !betas || !steps || !b_norm)
+      fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    set_device(op);
+    check_b(op, b, b_len);
+    check_k(k);
+    HostDecomp d;
+    if (!cb) {
+      if (reorth < 0 || reorth > 2) fail(TPL_ERR_INVALID_ARGUMENT, "reorth must be 0, 1 or 2");
+      run_pass_one(op, b, k, mem, true, reorth);
+      d = fetch_decomp(op);
+    } else {
+      // src/algorithms/lanczos.rs:86-128 with the host callback after every step, polled
+      // in batches: the device runs a batch of steps ahead (1, 2, 4, ... up to
+      // kCbBatchMax steps: at most as many speculative steps as were already confirmed),
+      // then the callback sees steps j = first .. last of the batch in order, each with
+      // the T_j view of that step (alphas[0..j), betas[0..j-1)) and V's first j columns.
+      // A stop at step j truncates the decomposition to j steps: later steps never change
+      // earlier alphas, betas or columns, so the result is exactly the one-step-at-a-time
+      // result, with one host synchronisation per batch instead of per step.
+      ensure_state(op, k, reorth != 0);
+      ensure_basis(op, k);
+      // the callback's view in the caller's row order: each batch's new columns are
+      // gathered into it (reordered operators only)
+      double* Vview = ensure_view(op, k);
+      upload_vec(op, op->b, b, mem);
+      enqueue_p1_prologue(op);
+      size_t stop_at = k;
+      int batch = 1;
+      for (int j0 = 1; j0 <= (int)k;) {
+        const int j1 = std::min<int>((int)k, j0 + batch - 1);
+        for (int j = j0; j <= j1; ++j) {
+          enqueue_p1_step(op, j, (int)k, op->d_V + (size_t)(j - 1) * op->part.n);
+          if (reorth && j < (int)k) enqueue_reorth(op, j, reorth);
+        }
+        if (Vview != op->d_V)
+          HIPCHK(launch::permute(op->part.n, j1 - j0 + 1,
+                                 Vview + (size_t)(j0 - 1) * op->part.n, op->part.n,
+                                 op->d_V + (size_t)(j0 - 1) * op->part.n, op->part.n,
+                                 op->bufs.d_iperm, op->stream));
+        d = fetch_decomp(op);
+        bool go = true;
+        for (int j = j0; j <= j1 && go; ++j) {
+          if (d.flags[0] && d.steps < (size_t)j) {  // zero b, or breakdown before step j
+            stop_at = d.steps;
+            go = false;
+            break;
+          }
+          go = cb((size_t)j, Vview, op->part.n, d.alphas, (size_t)j, d.betas, (size_t)j - 1,
+                  cb_user) != 0;
+          if (!go) stop_at = (size_t)j;
+        }
+        if (!go) break;
+        j0 = j1 + 1;
+        batch = std::min(2 * batch, kCbBatchMax);
+      }
+      d = fetch_decomp(op);
+      d.steps = std::min(d.steps, stop_at);
+    }
+    write_decomp(d, alphas, betas, steps, b_norm);
+    // second passes of the steps the caller keeps: a step callback may stop before the
+    // device's last step (batched polling runs ahead), so count the kept steps' records
+    op->reorth_second = reorth == 1 && d.steps > 1 ? (int64_t)d.steps - 1 : 0;
+    if (reorth == 2 && d.steps > 1) {
+      std::vector<int> rec(d.steps - 1);
+      HIPCHK(hipMemcpy(rec.data(), reorth_records(op), rec.size() * sizeof(int),
+                       hipMemcpyDeviceToHost));
+      for (int r : rec) op->reorth_second += r;
+    }
+    if (v_out && d.steps > 0) {
+      download_vec(op, v_out, op->d_V, (int64_t)d.steps, mem);
+      sync_checked(op);
+    }
+  });
+}
+
+tpl_status tpl_lanczos_pass_two(tpl_op_t op, const double* b, int64_t b_len, const double* alphas,
+                                size_t n_alphas, const double* betas, size_t n_betas,
+                                size_t steps, double b_norm, const double* y, size_t y_len,
+                                double* x_out, double* v_out, int mem) {
+  return guarded([&] {
+    if (!op || !x_out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    set_device(op);
+    check_b(op, b, b_len);
+    // src/algorithms/lanczos_two_pass.rs:220-227
+    if (steps != y_len) fail_param_mismatch("y_k", steps, y_len);
+    // :229-235
+    if (b_norm <= kBreakdownTol)
+      fail_input("The initial vector `b` must not be a zero vector.");
+    if (steps == 0) { // :237-244
+      zero_out(op, x_out, mem);
+      return;
+    }
+    if (n_alphas < steps || n_betas + 1 < steps || !alphas || (steps > 1 && !betas) || !y)
+      fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
+    ensure_state(op, steps);
+    // decomposition -> device: norms[0], alphas, betas, y
+    const DevState& S = op->st.S;
+    HIPCHK(hipMemcpyAsync(S.norms, &b_norm, sizeof(double), hipMemcpyHostToDevice, op->stream));
+    HIPCHK(hipMemcpyAsync(S.alphas, alphas, steps * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    if (steps > 1)
+      HIPCHK(hipMemcpyAsync(S.betas, betas, (steps - 1) * sizeof(double), hipMemcpyHostToDevice,
+                            op->stream));
+    HIPCHK(hipMemcpyAsync(S.y, y, steps * sizeof(double), hipMemcpyHostToDevice, op->stream));
+    upload_vec(op, op->b, b, mem);
+    if (v_out) {
+      ensure_basis(op, steps);
+      enqueue_pass2(op, steps, op->d_V);
+    } else {
+      run_pass2(op, steps);
+    }
+    download_vec(op, x_out, op->x, 1, mem);
+    if (v_out) download_vec(op, v_out, op->d_V, (int64_t)steps, mem);
+    sync_checked(op);
+  });
+}
+
+tpl_status tpl_lanczos_two_pass(tpl_op_t op, const double* b, int64_t b_len, size_t k,
+                                tpl_ftk_fn f, void* f_user, double* x_out, int mem) {
+  return guarded([&] {
+    if (!op || !x_out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    set_device(op);
+    check_b(op, b, b_len);
+    check_k(k);
+    // the built-in inv / exp on the device: the whole solve one graph (pass one, f(T_k)
+    // from the device alpha / beta, pass two), no host round trip between the passes
+    const DevF dev_f = device_f(op, f, k);
+    bool have_p1 = false;  // pass one already ran (the device handed f back to the host)
+    if (dev_f != kDevHost) {
+      // inv: the host solver's operations in its order, bit for bit (src/solvers.rs:148-174);
+      // exp: a parallel evaluation of the same function (k_ftk_exp), EVD-class accuracy
+      ensure_state(op, k);
+      upload_vec(op, op->b, b, mem);
+      run_two_pass_dev(op, k, dev_f);
+      download_vec(op, x_out, op->x, 1, mem);
+      HIPCHK(hipMemcpyAsync(op->st.h_state, op->st.d_state, kFlagBytes, hipMemcpyDeviceToHost,
+                            op->stream));
+      sync_checked(op);
+      int32_t flags[kFlagBytes / 4];
+      std::memcpy(flags, op->st.h_state, kFlagBytes);
+      if (zero_result(op, flags, x_out, mem) || !flags[4]) {
+        op->last_one_graph = true;
+        return;
+      }
+      // the device handed f(T_k) back (T_k not finite, or a spectrum too wide for the
+      // expansion): the host solver on the same decomposition, then pass two again
+      have_p1 = true;
+    }
+    // 1. pass one (src/solvers.rs:148)
+    op->last_one_graph = false;
+    if (!have_p1) run_pass_one(op, b, k, mem, false, false);
+    // 2. f(T_k) e_1 on the host (:155-165), 3. y = y' * ||b|| (:169)
+    const size_t steps = host_ftk(op, fetch_decomp(op), f, f_user, true, x_out, mem);
+    if (steps == 0) return;
+    // 4. pass two (:174)
+    run_pass2(op, steps);
+    download_vec(op, x_out, op->x, 1, mem);
+    sync_checked(op);
+  });
+}
+
+tpl_status tpl_lanczos(tpl_op_t op, const double* b, int64_t b_len, size_t k, tpl_ftk_fn f,
+                       void* f_user, double* x_out, int mem) {
+  return guarded([&] {
+    if (!op || !x_out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    set_device(op);
+    check_b(op, b, b_len);
+    check_k(k);
+    // the built-in inv / exp on the device after the standard pass, then the
+    // reconstruction: no host round trip (the same rules as tpl_lanczos_two_pass; y'
+    // unscaled, the GEMV multiplies by ||b||)
+    const DevF dev_f = device_f(op, f, k);
+    // 1. standard pass, V_k in HBM (src/solvers.rs:61); a device inv's LU eliminated
+    //    during it
+    run_pass_one(op, b, k, mem, true, false, dev_f == kDevInv);
+    op->last_one_graph = false;
+    if (dev_f != kDevHost) {
+      enqueue_ftk_only(op, k, dev_f, 0);
+      HIPCHK(launch::gemv_recon(op->part.n, -1, op->st.S, op->d_V, op->x, op->stream));
+    }
+    const HostDecomp d = fetch_decomp(op);
+    if (dev_f != kDevHost && !d.flags[1] && d.steps > 0 && !d.flags[4]) {
+      op->last_one_graph = true;  // the device's result stands
+      download_vec(op, x_out, op->x, 1, mem);
+      sync_checked(op);
+      return;
+    }
+    // 2. y' = f(T_k) e_1 on the host (a device exp may hand back: the same V_k) (:71-85)
+    const size_t steps = host_ftk(op, d, f, f_user, false, x_out, mem);
+    if (steps == 0) return;
+    // 3. x = ||b|| V_k y' (:96-104)
+    HIPCHK(launch::gemv_recon(op->part.n, (int)steps, op->st.S, op->d_V, op->x, op->stream));
+    download_vec(op, x_out, op->x, 1, mem);
+    sync_checked(op);
+  });
+}
+
+tpl_status tpl_op_reorth_second_passes(tpl_op_t op, int64_t* count) {
+  return guarded([&] {
+    if (!op || !count) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    *count = op->reorth_second;
+  });
+}
+
+tpl_status tpl_op_set_device_ftk(tpl_op_t op, int mode) {
+  return guarded([&] {
+    if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
+    if (mode < 0 || mode > 2) fail(TPL_ERR_INVALID_ARGUMENT, "device f(T_k) mode must be 0, 1 or 2");
+    op->device_ftk = mode;
+  });
+}
+
+tpl_status tpl_op_ftk_device(tpl_op_t op, int which, const double* alphas, size_t n,
+                             const double* betas, double* y_out, int* on_device) {
+  return guarded([&] {
+    if (!op || !alphas || !y_out || !on_device || (n > 1 && !betas))
+      fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (which != 0 && which != 1) fail(TPL_ERR_INVALID_ARGUMENT, "which must be 0 (inv) or 1 (exp)");
+    if (n == 0) fail(TPL_ERR_INVALID_ARGUMENT, "n must be >= 1");
+    if (n > (which == 0 ? kDevFtkMaxK : kDevExpMaxK))
+      fail(TPL_ERR_UNSUPPORTED, "k above the device f(T_k) bound");
+    set_device(op);
+    ensure_state(op, n);
+    // the solver state as pass one leaves it: steps_taken = n, ||b|| = 1, no error
+    int32_t flags[kFlagBytes / 4] = {0, 0, (int32_t)n, 0, 0, 0, 0, 0};
+    const double one = 1.0;
+    const DevState& S = op->st.S;
+    HIPCHK(hipMemcpyAsync(S.flags, flags, kFlagBytes, hipMemcpyHostToDevice, op->stream));
+    HIPCHK(hipMemcpyAsync(S.norms, &one, sizeof(double), hipMemcpyHostToDevice, op->stream));
+    HIPCHK(hipMemcpyAsync(S.alphas, alphas, n * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    if (n > 1)
+      HIPCHK(hipMemcpyAsync(S.betas, betas, (n - 1) * sizeof(double), hipMemcpyHostToDevice,
+                            op->stream));
+    enqueue_ftk_only(op, n, which == 1 ? kDevExp : kDevInv, 1);
+    HIPCHK(hipMemcpyAsync(y_out, S.y, n * sizeof(double), hipMemcpyDeviceToHost, op->stream));
+    HIPCHK(hipMemcpyAsync(flags, S.flags, kFlagBytes, hipMemcpyDeviceToHost, op->stream));
+    sync_checked(op);
+    *on_device = flags[4] ? 0 : 1;
+  });
+}
+
+} // extern "C"
