@@ -65,7 +65,7 @@ SOLVERS = {"inv": inv, "exp": exp, "sq": sq}
 
 
 def exp_chebyshev(alphas, betas, shifts: int = 256) -> np.ndarray:
-    """Restatement of the device exp (two-pass-lanczos_amd/csrc/tpl_kernels.hip k_ftk_exp)
+    """Restatement of the device exp (two-pass-lanczos_amd/csrc/tpl_k_ftk_exp.hip k_ftk_exp)
     in numpy — TEST INFRASTRUCTURE: it checks the algorithm (Sturm multisection bracket,
     Debye-sized Chebyshev expansion, Clenshaw + Miller's backward Bessel recurrence)
     against LAPACK on the CPU; the device's bits are not reproduced (libm exp/asinh differ).

@@ -103,7 +103,7 @@ static void spmv_faithful(const ocsr* A, const double* x, double* y) {
  * g + 8q, butterfly over the 8 lanes (xor 1, 2, 4); a longer piece: lane g (0..15) sums
  * its entries g + 16q, butterfly over 16 lanes. -> P_s; y = 0; y += P_s (s ascending). S: the
  * schedule's slice count (tpl_layout.cpp auto_slices).
- * (device: long_bin in tpl_kernels.hip; kBigPiece in tpl_device.h) */
+ * (device: long_bin in tpl_kcommon.h; kBigPiece in tpl_device.h) */
 #define BIG_PIECE 64
 static double long_row_canon(const ocsr* A, int32_t i, const double* x, int S) {
   const int64_t n = ncols_of(A);
@@ -202,7 +202,7 @@ static double nrm2_faithful(int64_t n, const double* x) {
 
 /* ------------------------------------------------------------ re-orthogonalisation */
 /* CGS2 of r against V[:, 0..cols) (column-major, ld = n), device order
- * (k_reorth_dot / k_reorth_reduce / k_reorth_update in tpl_kernels.hip): per pass,
+ * (k_reorth_dot / k_reorth_reduce / k_reorth_update in tpl_k_dist_reorth.hip): per pass,
  * h[c] = partials() of the G2 workgroup trees (workgroup b, thread t: acc = fma(V[c][i],
  * r[i], acc) over i = bE + t + 256q; tree256), then r[i] = r[i] - s_i with s_i = 0;
  * s_i = fma(V[c][i], h[c], s_i), c ascending. (Extension: the reference has no

@@ -16,7 +16,7 @@ cp "$ROOT/include/"*.h "$W/include/"
 (cd "$W/two-pass-lanczos_amd/csrc" && python3 "$edit")
 mkdir -p "$ROOT/two-pass-lanczos_amd/variants"
 base="-O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Wno-unused-value"
-make -s -C "$W/two-pass-lanczos_amd/csrc" OUT="$ROOT/two-pass-lanczos_amd/variants/libtpl_$name.so" \
+make -s -j16 -C "$W/two-pass-lanczos_amd/csrc" OUT="$ROOT/two-pass-lanczos_amd/variants/libtpl_$name.so" \
      CXXFLAGS="$base $extra" > "$W/build.log" 2>&1 || { tail -30 "$W/build.log"; exit 1; }
 (cd "$W/two-pass-lanczos_amd/csrc" && /opt/rocm/bin/hipcc $base $extra --offload-arch=gfx950 \
    -munsafe-fp-atomics --cuda-device-only -c tpl_kernels.hip -o /dev/null \

@@ -16,10 +16,10 @@ For every kernel named on the command line this reports
 usage: entry_trips.py [--asm FILE.s] [--json] KERNEL [KERNEL ...]
        KERNEL as in the source, e.g. 'k_p1_spmv<58>' or 'k_p1_axpy<12>'.
 
-Without --asm the newest two-pass-lanczos_amd/csrc/build/*.s that is not older than the
-kernel sources is used (`make asm` writes one); when there is none, tpl_kernels.hip is
-compiled device-only with the Makefile's flags into csrc/build/tpl_kernels.s (about two
-minutes).
+Without --asm the kernels are looked up in two-pass-lanczos_amd/csrc/build/all_units.asm,
+every unit's build/<unit>.s joined (`make asm` writes them: a kernel is found whichever
+unit holds it). When it is missing or older than the kernel sources, `make asm` is run
+first, with at most 16 jobs (about half a minute).
 """
 import argparse
 import glob
@@ -35,51 +35,28 @@ CSRC = os.path.join(ROOT, "two-pass-lanczos_amd", "csrc")
 
 
 # ------------------------------------------------------------------ the assembly file
-def _make_var(text, name, default=""):
-    m = re.search(r"^%s\s*\??=\s*(.*)$" % re.escape(name), text, re.M)
-    return m.group(1).strip() if m else default
-
-
-def makefile_flags():
-    """(hipcc, flags) of the Makefile's device compile line."""
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    arch = os.environ.get("ARCH") or _make_var(text, "ARCH", "gfx950")
-    hipcc = os.environ.get("HIPCC") or _make_var(text, "HIPCC", "hipcc")
-    flags = (_make_var(text, "CXXFLAGS") + " " + _make_var(text, "DEVFLAGS")).replace("$(ARCH)", arch)
-    return hipcc, flags.split()
-
-
-def sources():
-    return ([os.path.join(CSRC, "Makefile")] + glob.glob(os.path.join(CSRC, "*.hip")) +
-            glob.glob(os.path.join(CSRC, "tpl_*.h")))
+ALL_UNITS = os.path.join(CSRC, "build", "all_units.asm")  # `make asm`: every <unit>.s, joined
 
 
 def fresh_asm():
-    """The newest csrc/build/*.s holding gfx950 kernels that is not older than the sources."""
-    newest_src = max(os.path.getmtime(p) for p in sources())
-    best = None
-    for p in glob.glob(os.path.join(CSRC, "build", "*.s")):
-        mt = os.path.getmtime(p)
-        if mt < newest_src or (best and mt <= best[0]):
-            continue
-        with open(p, errors="replace") as f:
-            if ".amdhsa_kernel" in f.read():
-                best = (mt, p)
-    return best[1] if best else None
+    """ALL_UNITS, or None when it is missing or older than the kernel sources."""
+    newest_src = max(os.path.getmtime(p) for p in
+                     [os.path.join(CSRC, "Makefile")] + glob.glob(os.path.join(CSRC, "*.hip")) +
+                     glob.glob(os.path.join(CSRC, "tpl_*.h")))
+    if os.path.exists(ALL_UNITS) and os.path.getmtime(ALL_UNITS) >= newest_src:
+        return ALL_UNITS
+    return None
 
 
 def have_hipcc():
-    hipcc, _ = makefile_flags()
-    return bool(shutil.which(hipcc))
+    return bool(shutil.which(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")))
 
 
 def compile_asm():
-    hipcc, flags = makefile_flags()
-    out = os.path.join(CSRC, "build", "tpl_kernels.s")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = [hipcc] + flags + ["--cuda-device-only", "-S", "tpl_kernels.hip", "-o", out]
-    subprocess.run(cmd, cwd=CSRC, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
-    return out
+    jobs = str(min(16, os.cpu_count() or 4))
+    subprocess.run(["make", "-C", CSRC, "-j", jobs, "asm"], check=True,
+                   stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
+    return ALL_UNITS
 
 
 def asm_path():
@@ -262,7 +239,7 @@ def report(text, kernel):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--asm", help="assembly file (default: csrc/build/*.s, compiled if stale)")
+    ap.add_argument("--asm", help="assembly file (default: csrc/build/all_units.asm, built if stale)")
     ap.add_argument("--json", action="store_true", help="one JSON list instead of the table")
     ap.add_argument("kernels", nargs="+")
     a = ap.parse_args(argv)

@@ -33,7 +33,7 @@ assert OLD2 in s
 s = s.replace(OLD2, NEW2)
 open(p, "w").write(s)
 
-p = "tpl_kernels.hip"
+p = "tpl_klaunch.h"
 s = open(p).read()
 OLD3 = "? (size_t)A.bin_cap * sizeof(double) + kTPB * sizeof(int) + kTPB * sizeof(double)"
 NEW3 = "? (size_t)A.bin_cap * sizeof(double) + kTPB * sizeof(int) + (kTPB + 1) * sizeof(double)"

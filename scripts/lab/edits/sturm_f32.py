@@ -1,7 +1,7 @@
 # Lab edit: the device exp's Sturm bracket in single precision on T / max|Gershgorin end|
 # (entries in [-1, 1], beta^2 <= 4), the bracket widened by 1e-5 * gmag for fp32's backward
 # error (a count is exact for a matrix within a few ulps of the scaled T).
-s = open('tpl_kernels.hip').read()
+s = open('tpl_k_ftk_exp.hip').read()
 a = '''  const double pivmin = 2.2250738585072014e-308 * fmax(1.0, red[0][0]);'''
 assert a in s
 s = s.replace(a, a + '''
@@ -66,4 +66,4 @@ s = s.replace(a, '''  const double a = (first[0] > 0 ? glo + wsh * (double)first
 a = '''                   1e-9 * (1.0 + gmag);'''
 assert a in s
 s = s.replace(a, '''                   1e-9 * (1.0 + gmag) + 1e-5 * gmag;''')
-open('tpl_kernels.hip', 'w').write(s)
+open('tpl_k_ftk_exp.hip', 'w').write(s)

@@ -1,6 +1,6 @@
 // spmv_lab2.hip — the library's k_spmv (included verbatim) vs a minimal SELL kernel,
 // on the 500k KKT arc rows only. Build with -DTPL_CHUNK_ROWS=256.
-#include "../two-pass-lanczos_amd/csrc/tpl_kernels.hip"
+#include "../two-pass-lanczos_amd/csrc/tpl_k_spmv.hip"
 #include <cstdio>
 #include <vector>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)

@@ -1,8 +1,8 @@
 """CPU: the headline kernels fetch their arguments in one scalar round trip.
 
-scripts/entry_trips.py reads the compiled gfx950 assembly (an existing csrc/build/*.s when
-the kernel sources are not newer, else a device-only compile with the Makefile's flags,
-about two minutes). For k_spmv<58>, k_p1_spmv<58>, k_p2_spmv<58> and every k_p1_axpy<NP>:
+scripts/entry_trips.py reads the compiled gfx950 assembly (csrc/build/all_units.asm, every
+unit's assembly joined, when the kernel sources are not newer, else `make asm` first,
+about half a minute). For k_spmv<58>, k_p1_spmv<58>, k_p2_spmv<58> and every k_p1_axpy<NP>:
 
   * no kernel-argument load after the first `s_waitcnt lgkmcnt(0)`, outside the allow-list
     below — and no allow-listed one either on a path that has not issued a vector load yet;

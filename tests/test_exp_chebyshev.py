@@ -1,4 +1,4 @@
-"""CPU: the device exp(T_k) e_1 algorithm (tpl_kernels.hip k_ftk_exp), restated in numpy
+"""CPU: the device exp(T_k) e_1 algorithm (tpl_k_ftk_exp.hip k_ftk_exp), restated in numpy
 (oracle/ftk_ref.py exp_chebyshev), against LAPACK's EVD (the reference's method,
 src/bin/stability.rs:175-193). Tolerance stated in tests/test_gpu_device_exp.py: for every
 case the algorithm keeps (it hands ||y|| < 1e-3 exp(lambda_max) back to the host),

@@ -3,7 +3,7 @@ exp solve it enables.
 
 The reference forms exp(T_k) e_1 = Q exp(Lambda) Q^T e_1 from a dense EVD
 (src/bin/stability.rs:175-193). The device evaluates the same function with a Chebyshev
-expansion over the Sturm-bracketed spectrum (tpl_kernels.hip k_ftk_exp). Its contract is
+expansion over the Sturm-bracketed spectrum (tpl_k_ftk_exp.hip k_ftk_exp). Its contract is
 a tolerance, not bits: an EVD-based result carries an error of a few eps * ||T|| *
 exp(lambda_max) (backward stability), the expansion a few eps * (terms) * exp(lambda_max).
 Stated tolerance: ||y_dev - y_lapack|| <= TOL_SCALE * exp(lambda_max) (TOL_SCALE =

@@ -1,4 +1,4 @@
-// tpl_device.h — structures shared by the HIP kernels (tpl_kernels.hip) and the
+// tpl_device.h — structures shared by the HIP kernels (map: tpl_kernels.hip) and the
 // host units (tpl_op.h). Everything here is plain data: the kernels take
 // these structs by value as kernel arguments.
 //
@@ -261,6 +261,14 @@ struct P1SpmvArgs {
   unsigned int* Pcnt;
   double* ypart;
 };
+// The CsrDev fields P1SpmvArgs carries, under the same names: the launcher copies them in
+// (tpl::launch::p1_spmv), the kernel's CsrDev view copies them back (layout_of). A field
+// named here once is in both copies.
+#define TPL_P1_LAYOUT_FIELDS(X)                                                             \
+  X(srows) X(s_col) X(s_cbase) X(s_val) X(c_base) X(c_width) X(b_col) X(b_cbase) X(b_val)   \
+  X(b_seg) X(b_hdr) X(P) X(Pcnt) X(s_width) X(s_identity) X(n_short) X(n_chunks) X(bin_cap) \
+  X(n_slice_blocks) X(G2) X(G2_r) X(pb_ld) X(n_slices) X(E) X(ypart) X(long_defer)          \
+  X(s_win) X(s_win_max)
 
 struct P1AxpyArgs {
   const double* Pa_r;       // DevState

@@ -1,6 +1,6 @@
-// tpl_kcommon.h — device building blocks of the kernels (tpl_kernels.hip): DPP
-// reductions, epilogues, the sliced-ELL chunk and the long-row bin. Included only by
-// .hip files.
+// tpl_kcommon.h — device building blocks of the kernels (map: tpl_kernels.hip): DPP
+// reductions, epilogues, the sliced-ELL chunk and the long-row bin, the variant flag of the
+// SpMV-shaped kernels, the pass-one step's SpMV body. Included only by .hip files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "tpl_device.h"
@@ -215,6 +215,21 @@ struct EpiPass2R {
   double* v_next;
   double* x;
   double* Vcol;
+  // from the arguments of a pass-two step kernel (k_p2_spmv, k_long_epi_p2)
+  static __device__ __forceinline__ EpiPass2R of(const double* rec, const double* v_cur,
+                                                 const double* v_prev, double* v_next,
+                                                 double* x, double* Vcol, int j, int nflush) {
+    EpiPass2R epi;
+    epi.v_cur = v_cur;
+    epi.v_prev = (j >= 2) ? v_prev : v_cur;
+    epi.rec = rec;
+    epi.has_prev = j >= 2;
+    epi.nflush = nflush;
+    epi.v_next = v_next;
+    epi.x = x;
+    epi.Vcol = Vcol;
+    return epi;
+  }
   __device__ __forceinline__ Pre2R pre(int i) const {
     return Pre2R{v_cur[i], v_prev[i], nflush ? x[i] : 0.0, rec[threadIdx.x & 7]};
   }
@@ -756,10 +771,28 @@ __device__ __forceinline__ int chunk_of_block(const CsrDev& A, int i) {
 
 // Minimum waves per SIMD requested for the SpMV-shaped kernels (occupancy vs VGPRs).
 constexpr int kSpmvMinWaves = 1;
+// The variant flag F of the SpMV-shaped kernels: one instance per layout format.
+constexpr int kVarWidth = 7;    // mask: the uniform chunk width 1..4 (0: any per-chunk width)
+constexpr int kVarVal8 = 8;     // int8 values
+constexpr int kVarSCol16 = 16;  // uint16 column offsets in the chunks
+constexpr int kVarBCol16 = 32;  // uint16 column offsets in the bins
+constexpr int kVarWin = 64;     // chunk column window in LDS
+constexpr int kVarEnd = 128;    // F < kVarEnd
+// The instances that exist: width 0..4, and the window only with a uniform width and
+// uint16 chunk columns (tpl::launch::variant_of computes no other value).
+constexpr bool variant_exists(int F) {
+  return F >= 0 && F < kVarEnd && (F & kVarWidth) <= 4 &&
+         (!(F & kVarWin) || ((F & kVarWidth) > 0 && (F & kVarSCol16)));
+}
+constexpr int count_variants() {
+  int c = 0;
+  for (int F = 0; F < kVarEnd; ++F) c += variant_exists(F);
+  return c;
+}
+static_assert(count_variants() == 56, "5 widths x 8 formats + 4 widths x 4 formats with the window");
 // Grid: [bins of the long rows][short chunks] (or chunks first). Returns the chunk
 // index whose alpha partial this workgroup owns, or -1.
-// F = CW | V8 << 3 | SC16 << 4 | BC16 << 5 | WIN << 6: uniform chunk width (0: any), int8
-// values, uint16 column offsets in the chunks / in the bins, chunk column window in LDS.
+// F = width (kVarWidth) | kVarVal8 | kVarSCol16 | kVarBCol16 | kVarWin.
 template <int F, class Epi, class ScaleFn>
 __device__ __forceinline__ int spmv_block_impl(const CsrDev& A, const double* __restrict__ xsrc,
                                                ScaleFn scale_of, const Epi& epi, double& acc,
@@ -777,12 +810,13 @@ __device__ __forceinline__ int spmv_block_impl(const CsrDev& A, const double* __
       m = b / A.n_slices;
       s = b % A.n_slices;
     }
-    long_bin<((F >> 3) & 1), ((F >> 5) & 1)>(A, m, s, xsrc, scale_of, epi, lds);
+    long_bin<(F & kVarVal8) != 0, (F & kVarBCol16) != 0>(A, m, s, xsrc, scale_of, epi, lds);
     return -1;
   }
   const int chunk = chunk_of_block(A, b - A.n_slice_blocks);
   if (chunk < 0) return -1;  // grid padding
-  return short_chunk<(F & 7), ((F >> 3) & 1), ((F >> 4) & 1), ((F >> 6) & 1)>(A, chunk, xsrc, scale_of, epi, acc, lds)
+  return short_chunk<(F & kVarWidth), (F & kVarVal8) != 0, (F & kVarSCol16) != 0,
+                     (F & kVarWin) != 0>(A, chunk, xsrc, scale_of, epi, acc, lds)
              ? chunk : -1;
 }
 
@@ -795,6 +829,165 @@ __device__ __forceinline__ int spmv_block(const CsrDev& A, const double* __restr
   const int r = spmv_block_impl<F>(A, xsrc, scale_of, epi, acc, lds);
   TPL_MARK(5);
   return r;
+}
+
+// ------------------------------------------------------ the pass-one step's SpMV
+// (k_p1_spmv in tpl_kernels.hip, k_p1_spmv_gp and k_p1_spmv_wide in units of their own)
+// Pass one / standard, step j >= 1. r_cur = r_j (== b at j = 1), this rank's rows;
+// xsrc = the gather source holding r_j for every column (== r_cur on one GPU, the
+// all-gathered vector when the rows are partitioned over ranks).
+// beta_{j-1} comes from the G2_r norm partials k_p1_axpy left: NBP per thread (1 when
+// G2_r <= 256, the usual case; 4 up to 1024), loaded at entry ahead of the entries and
+// gathers, reduced in scale_fn once they are in flight. The registers of those loads stay
+// live across the whole SpMV, so they set the kernel's occupancy: with one partial per
+// thread (the wave totals exchanged through LDS behind one barrier) k_p1_spmv<58> needs
+// 58 VGPRs, 8 waves per SIMD, and the 1,560-workgroup grid at 500k arcs is resident at
+// once; with four per lane (each wave reducing all 256 itself, no barrier: r03) it needed
+// 76 (6 waves): 24 workgroups waited for a slot and the chunks started at 1.8 us (median)
+// instead of 0.4 (stamps, scripts/stamps.py). Same box, alternated three times: solve
+// 9.12-9.17 vs 9.50-9.56 ms, pass one 11.35-11.45 vs 12.17-12.21 us per step, isolated
+// k_p1_spmv 6.60-6.67 vs 7.46-7.68 us; the tree and so the bits are the same.
+constexpr int p1_min_waves(int F, int NBP) {
+  return (NBP > 1 && (F & kVarVal8) && ((F & kVarWidth) == 1 || (F & kVarWidth) == 2))
+             ? 6 : kSpmvMinWaves;
+}
+// The SpMV building blocks (tpl_kcommon.h) read the layout through a CsrDev: the view of
+// the fields the kernel argument carries. The fields no SpMV path reads stay zero and are
+// never materialised (every user is inlined).
+__device__ __forceinline__ CsrDev layout_of(const P1SpmvArgs& a) {
+  CsrDev A{};
+#define TPL_FIELD(f) A.f = a.f;
+  TPL_P1_LAYOUT_FIELDS(TPL_FIELD)
+#undef TPL_FIELD
+  return A;
+}
+template <int F, int NBP>
+__device__ __forceinline__ void p1_spmv_body(const P1SpmvArgs& a, double* red, double* redb,
+                                             double* lds, double* redr = nullptr) {
+  // Every kernel argument a path reads ahead of its first vector load is fetched by the
+  // entry batch of scalar loads, before any branch on one of them (hipcc sinks an
+  // argument's load into the branch that uses it: a dependent scalar round trip there).
+  // The layout fields, E and G2 (chunk_of_block) included, and the launch stamp's pointer;
+  // scripts/entry_trips.py checks the compiled code for loads behind the first wait. Left
+  // to load where they are used, behind the bin's vector loads: the hand-off's fields (P,
+  // Pcnt, long_defer, ypart) — fetched at entry as well they take k_p1_spmv<58> to 82 SGPRs.
+  const CsrDev A = layout_of(a);
+  struct {
+    const double* Pb_r; int32_t* flags; double* norms; double* betas; double* Pa;
+  } S{a.Pb_r, a.flags, a.norms, a.betas, a.Pa};
+  const double* __restrict__ xsrc = a.xsrc;
+  const double* __restrict__ r_cur = a.r_cur;
+  const double* __restrict__ r_prev = a.r_prev;
+  double* __restrict__ W = a.W;
+  double* __restrict__ Vcol = a.Vcol;
+  const int j = a.j;
+  unsigned long long* stamp = a.stamp;
+  pin_layout_args(A);
+  asm volatile("" ::"s"(A.E), "s"(A.G2), "s"(A.srows));
+  if constexpr ((F & kVarWidth) == 0)
+    asm volatile("" ::"s"(A.c_base), "s"(A.c_width), "s"(A.s_width));
+  if constexpr ((F & kVarWin) != 0) asm volatile("" ::"s"(A.s_win), "s"(A.s_win_max));
+  if constexpr (NBP < 0) asm volatile("" ::"s"(A.pb_ld));
+  asm volatile("" ::"s"(S.Pb_r), "s"(S.flags), "s"(S.norms), "s"(S.betas), "s"(S.Pa), "s"(A.G2_r),
+               "s"(xsrc), "s"(r_cur), "s"(r_prev), "s"(W), "s"(Vcol), "s"(j), "s"(stamp));
+  launch_stamp(stamp);
+  PartialRegs<(NBP > 0 ? NBP : -NBP)> pr;
+  if constexpr (NBP > 0) {
+    load_partials(S.Pb_r, A.G2_r, pr);
+  } else {
+    // NBP = -kPbRanks (replicated partition, round 6): every rank's norm partials,
+    // all-gathered pb_ld apart and zero-padded; lane t loads partial t of each rank
+    const int ld = A.pb_ld, R = A.G2_r;
+#pragma unroll
+    for (int r = 0; r < -NBP; ++r)
+      pr.v[r] = S.Pb_r[(size_t)clampi(r, R - 1) * ld + clampi((int)threadIdx.x, ld - 1)];
+  }
+  // the stop flag and beta_{j-2} with the partials, ahead of the entries and gathers:
+  // read later, their wait would drain every gather in flight before the beta chain
+  int stop0 = S.flags[0];
+  double norm_prev = (j >= 2) ? S.norms[j - 2] : 1.0;
+  // keep these loads first: sunk below the gathers by the scheduler, their wait would
+  // again drain every gather before the beta chain
+  __builtin_amdgcn_sched_barrier(0);
+  EpiPass1 epi;
+  epi.r_cur = r_cur;
+  epi.r_prev = (j >= 2) ? r_prev : r_cur;
+  epi.has_prev = j >= 2;
+  epi.invN_prev = 0.0;
+  epi.invN_cur = 0.0;
+  epi.beta_sub = 0.0;
+  epi.W = W;
+  epi.Vcol = Vcol;
+  epi.Pa_long = S.Pa + A.n_chunks;
+  // beta_{j-1} (||b|| at j = 1) from the norm partials; fills the epilogue. Runs once the
+  // workgroup's loads are in flight.
+  auto scale_fn = [&]() -> Scale {
+    __builtin_amdgcn_sched_barrier(0);
+    // opaque here: the optimiser would otherwise hoist the stop test and the reciprocal
+    // to the loads, making every workgroup wait for them before issuing its entries
+    asm volatile("" : "+v"(stop0), "+v"(norm_prev));
+    if (stop0) return Scale{0.0, false};
+    epi.invN_prev = (j >= 2) ? 1.0 / norm_prev : 0.0;
+    // the canonical tree (s = 0; s += P[t + 256u]; tree256), one barrier: its LDS words
+    // (redb) are not reused, and the barrier waits for LDS traffic only, never for the
+    // gathers in flight
+    double beta;
+    if constexpr (NBP == 1) {
+      double sq = 0.0;
+      if ((int)threadIdx.x < A.G2_r) sq = sq + pr.v[0];
+      beta = sqrt(block_sum_tail(sq, redb));
+    } else if constexpr (NBP > 1) {  // any count (more than 256 NBP in batches)
+      beta = sqrt(finish_partials(S.Pb_r, A.G2_r, pr, redb));
+    } else {
+      // each rank's total by the tree the rank-total launch applied (k_reorth_reduce:
+      // s = 0; s += P[t]; wave sums; (S0 + S1) + (S2 + S3) — the zero padding adds +0.0 to
+      // +0.0), then the R totals exactly as the one-partial path above reduces the
+      // all-gathered totals: the bits of the rank-total launch + all-gather, one launch
+      // less per pass-one step. One barrier more than that path; it waits
+      // for LDS traffic only, never for the gathers in flight.
+      const int R = A.G2_r, ld = A.pb_ld;
+#pragma unroll
+      for (int r = 0; r < -NBP; ++r) {
+        if (r < R) {  // uniform
+          double sr = 0.0;
+          if ((int)threadIdx.x < ld) sr = sr + pr.v[r];
+          sr = wave_sum(sr);
+          if ((threadIdx.x & 63) == 0) redr[4 * r + (threadIdx.x >> 6)] = sr;
+        }
+      }
+      __syncthreads();
+      double sq = 0.0;
+      if ((int)threadIdx.x < R) {
+        const double* q = redr + 4 * threadIdx.x;
+        sq = sq + ((q[0] + q[1]) + (q[2] + q[3]));
+      }
+      beta = sqrt(block_sum_tail(sq, redb));
+    }
+    if (beta <= kBreakdownTol) {
+      // j == 1: zero b -> InputError (src/algorithms/mod.rs:267-273);
+      // j  > 1: breakdown -> steps_taken = j - 1, beta not pushed
+      //         (src/algorithms/lanczos_two_pass.rs:245-249).
+      if (blockIdx.x == 0 && threadIdx.x == 0) {
+        S.flags[0] = 1;
+        if (j == 1) S.flags[1] = 1;
+      }
+      return Scale{0.0, false};
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      S.norms[j - 1] = beta;
+      if (j >= 2) S.betas[j - 2] = beta;
+    }
+    epi.invN_cur = 1.0 / beta;
+    epi.beta_sub = (j >= 2) ? beta : 0.0;
+    return Scale{epi.invN_cur, true};
+  };
+  double acc = 0.0;
+  const int slot = spmv_block<F>(A, xsrc, scale_fn, epi, acc, lds);
+  if (slot < 0) return; // uniform per workgroup
+  const double p = block_sum_tail(acc, red);
+  // write-through: every k_p1_axpy workgroup, on every XCD, reads all the partials
+  // next (measured: pass one -0.2 to -0.3 us per step against a plain store)
+  if (threadIdx.x == 0) st_out(S.Pa + slot, p);
 }
 
 } // namespace tpl

@@ -1,11 +1,19 @@
 // tpl_lab.h — diagnostic instrumentation of the kernels, compiled in only by the stamp
 // build (scripts/diag.sh: -DTPL_STAMP=1). In the product build every hook is empty.
+// The mark table and its readers live in one unit, the one that defines TPL_LAB_TABLE
+// before including this header (tpl_kernels.hip: the headline's kernels); device variables
+// are not shared between units, so the hooks of the other units stay empty. To stamp a
+// kernel of another unit (k_ftk_exp for scripts/exp_lab.py), move the define there.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace tpl {
 
 #ifndef TPL_STAMP
+#define TPL_STAMP 0
+#endif
+#if TPL_STAMP && !defined(TPL_LAB_TABLE)
+#undef TPL_STAMP
 #define TPL_STAMP 0
 #endif
 #if TPL_STAMP

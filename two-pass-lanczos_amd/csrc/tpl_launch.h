@@ -1,5 +1,5 @@
-// tpl_launch.h — the kernel launchers: declared here once, defined in tpl_kernels.hip,
-// called by the host units. Each enqueues on `s` and returns the launch's status.
+// tpl_launch.h — the kernel launchers: declared here once, defined in the .hip unit that
+// holds the kernel (map: tpl_kernels.hip), called by the host units. Each enqueues on `s` and returns the launch's status.
 #pragma once
 #include <hip/hip_runtime.h>
 
