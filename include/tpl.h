@@ -317,6 +317,12 @@ tpl_status tpl_op_set_schedule(tpl_op_t op, int32_t short_row_max, int32_t max_g
  * more if a (row, slice) piece would not fit one bin).                          */
 tpl_status tpl_op_slices(tpl_op_t op, int32_t* slices);
 tpl_status tpl_op_set_slices(tpl_op_t op, int32_t slices);
+/* The variant flag F of the layout: which instance of the SpMV-shaped kernels (k_spmv<F>,
+ * k_p1_spmv<F> and its siblings, k_p2_spmv<F>) the launchers dispatch to. F = uniform
+ * chunk width 1..4 (0: the generic, per-chunk width) | 8 int8 values | 16 uint16 chunk
+ * columns | 32 uint16 bin columns | 64 chunk column window in LDS. Every instance
+ * computes the same bits; the tests use this to know which one they ran.             */
+tpl_status tpl_op_kernel_variant(tpl_op_t op, int32_t* variant);
 
 /* Second Gram-Schmidt passes of the last re-orthogonalised tpl_lanczos_standard call
  * (steps - 1 for CGS2; the count the selective mode actually ran).                */
@@ -439,8 +445,8 @@ tpl_status tpl_operand_key(int64_t n, const void* ptr_arr, size_t ptr_len, size_
  * the halo's bytes without a GPU), run by the same code: rank
  * `rank` of `nranks`, its rows, order and SpMV layout, and nothing on a device. Only
  * the host introspection calls accept the returned handle — tpl_op_nrows, tpl_op_nnz,
- * tpl_op_flags, tpl_op_schedule, tpl_op_slices, tpl_op_permutation, tpl_op_local_rows,
- * tpl_op_order_groups, tpl_kernel_algo_bytes — every other call returns
+ * tpl_op_flags, tpl_op_schedule, tpl_op_slices, tpl_op_kernel_variant, tpl_op_permutation,
+ * tpl_op_local_rows, tpl_op_order_groups, tpl_kernel_algo_bytes — every other call returns
  * TPL_ERR_INVALID_ARGUMENT; free it with tpl_op_destroy. The parity fixtures use it to
  * restate a run's reduction order on a host without a GPU (tests/golden/make_parity.py). */
 enum { TPL_PLAN_SINGLE = 0, TPL_PLAN_REPLICATED = 1, TPL_PLAN_ROWS = 2, TPL_PLAN_HALO = 3 };

@@ -2,11 +2,16 @@
 the HIP path, each checked BITWISE against the canonical oracle (P2): the SpMV, pass one
 (alphas, betas, steps, ||b||), the two-pass x, and the one-pass x.
 
-The shapes cover what the fixed tests do not: tiny and empty-row matrices, a single
+The shapes cover what the fixed tests do not: tiny matrices, a single
 long row, rows straddling the short/long threshold, many hubs that need several bins
 per slice, non-integer values (fp64 storage) and small integers (int8 storage), explicit
 short-row thresholds (wider sliced-ELL chunks, the generic chunk width), and every slice
 count. Seeds are fixed, so a failure names a reproducible case.
+
+There are no empty rows here (the generator always adds a diagonal), and most seeds run the
+generic-width kernel instance: empty rows and chunks, and every compiled instance, are
+pinned by tests/test_gpu_variants.py. Each failure message names the instance the seed ran
+(HipCsrOp.kernel_variant).
 """
 import numpy as np
 import pytest
@@ -69,16 +74,17 @@ def test_random_matrix_bitwise(seed):
     if slices:
         op.set_slices(slices)
     o = oracle.Operator(a, op.schedule())
+    F = f"F={op.kernel_variant()}"
     x = rng.standard_normal(n)
-    assert same_bits(op.apply(x), o.apply(x)), "spmv"
+    assert same_bits(op.apply(x), o.apply(x)), f"spmv, {F}"
     b = rng.standard_normal(n)
     k = int(min(rng.integers(1, 60), 4 * n + 1))
     d = alg.lanczos_pass_one(op, b, k)
     al, be, st, bn, _ = o.pass_one(b, k)
-    assert d.steps_taken == st and d.b_norm == bn
-    assert same_bits(d.alphas, al) and same_bits(d.betas, be)
+    assert d.steps_taken == st and d.b_norm == bn, F
+    assert same_bits(d.alphas, al) and same_bits(d.betas, be), F
     xt = solvers.lanczos_two_pass(op, b, k, ftk.INV)
-    assert same_bits(xt, o.lanczos_two_pass(b, k, ftk.INV)), "two-pass"
+    assert same_bits(xt, o.lanczos_two_pass(b, k, ftk.INV)), f"two-pass, {F}"
     xs = solvers.lanczos(op, b, k, ftk.INV)
-    assert same_bits(xs, o.lanczos(b, k, ftk.INV)), "one-pass"
+    assert same_bits(xs, o.lanczos(b, k, ftk.INV)), f"one-pass, {F}"
     op.close()

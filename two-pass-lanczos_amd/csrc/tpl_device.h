@@ -182,6 +182,23 @@ struct CsrDev {
   int32_t s_win_max;
 };
 
+// The variant flag F of the SpMV-shaped kernels (k_spmv<F>, k_p1_spmv<F> and its siblings,
+// k_p2_spmv<F>; tpl_kcommon.h variant_exists): one instance per layout format.
+constexpr int kVarWidth = 7;    // mask: the uniform chunk width 1..4 (0: any per-chunk width)
+constexpr int kVarVal8 = 8;     // int8 values
+constexpr int kVarSCol16 = 16;  // uint16 column offsets in the chunks
+constexpr int kVarBCol16 = 32;  // uint16 column offsets in the bins
+constexpr int kVarWin = 64;     // chunk column window in LDS
+constexpr int kVarEnd = 128;    // F < kVarEnd
+// The layout's variant flag (chunk width, value and column formats, column window): the
+// one rule, for the launchers' dispatch (tpl_klaunch.h TPL_LAUNCH_CW) and for
+// tpl_op_kernel_variant.
+inline int variant_of(const CsrDev& A) {
+  const int cw = A.s_width >= 1 && A.s_width <= 4 ? A.s_width : 0;
+  return cw | (A.val_i8 ? kVarVal8 : 0) | (A.s_col16 ? kVarSCol16 : 0) |
+         (A.b_col16 ? kVarBCol16 : 0) | (A.s_win > 0 && cw > 0 && A.s_col16 ? kVarWin : 0);
+}
+
 // Device-resident solver state (one per operator).
 constexpr int kFlagBytes = 32;       // DevState::flags: 8 int32
 struct DevState {

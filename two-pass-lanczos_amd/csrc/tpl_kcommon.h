@@ -771,15 +771,10 @@ __device__ __forceinline__ int chunk_of_block(const CsrDev& A, int i) {
 
 // Minimum waves per SIMD requested for the SpMV-shaped kernels (occupancy vs VGPRs).
 constexpr int kSpmvMinWaves = 1;
-// The variant flag F of the SpMV-shaped kernels: one instance per layout format.
-constexpr int kVarWidth = 7;    // mask: the uniform chunk width 1..4 (0: any per-chunk width)
-constexpr int kVarVal8 = 8;     // int8 values
-constexpr int kVarSCol16 = 16;  // uint16 column offsets in the chunks
-constexpr int kVarBCol16 = 32;  // uint16 column offsets in the bins
-constexpr int kVarWin = 64;     // chunk column window in LDS
-constexpr int kVarEnd = 128;    // F < kVarEnd
+// The variant flag F of the SpMV-shaped kernels (tpl_device.h kVar*, variant_of): one
+// instance per layout format.
 // The instances that exist: width 0..4, and the window only with a uniform width and
-// uint16 chunk columns (tpl::launch::variant_of computes no other value).
+// uint16 chunk columns (variant_of computes no other value).
 constexpr bool variant_exists(int F) {
   return F >= 0 && F < kVarEnd && (F & kVarWidth) <= 4 &&
          (!(F & kVarWin) || ((F & kVarWidth) > 0 && (F & kVarSCol16)));

@@ -30,12 +30,6 @@ static inline size_t spmv_lds_bytes(const CsrDev& A) {
   const size_t win = (size_t)A.s_win * sizeof(double);  // short-chunk column window
   return bins > win ? bins : win;
 }
-// The layout's variant flag (chunk width, value and column formats, column window).
-static inline int variant_of(const CsrDev& A) {
-  const int cw = A.s_width >= 1 && A.s_width <= 4 ? A.s_width : 0;
-  return cw | (A.val_i8 ? kVarVal8 : 0) | (A.s_col16 ? kVarSCol16 : 0) |
-         (A.b_col16 ? kVarBCol16 : 0) | (A.s_win > 0 && cw > 0 && A.s_col16 ? kVarWin : 0);
-}
 // launch_f(std::integral_constant<int, F>) for the F equal to f, over the instances that
 // exist; hipErrorInvalidConfiguration when f has none, else the launch's status.
 template <class LaunchF, int... Fs>
@@ -49,7 +43,8 @@ hipError_t dispatch_variant(int f, LaunchF launch_f, std::integer_sequence<int, 
   return (one(std::integral_constant<int, Fs>{}) || ...) ? hipGetLastError()
                                                           : hipErrorInvalidConfiguration;
 }
-// Launch the SpMV-shaped kernel specialised for the layout A, on stream s.
+// Launch the SpMV-shaped kernel specialised for the layout A (the instance of its variant
+// flag, tpl_device.h variant_of), on stream s.
 #define TPL_LAUNCH_CW(KERNEL, A, s, ...)                                                    \
   dispatch_variant(                                                                         \
       variant_of(A),                                                                        \

@@ -26,15 +26,23 @@ int long_epi_blocks(const tpl_op_s* op) {
   return (int)((op->lay.lrows.size() + kLongEpiRows - 1) / kLongEpiRows);
 }
 
-CsrDev csr_dev(const tpl_op_s* op, bool pass1) {
-  const Layout& L = op->lay;
-  CsrDev A;
-  A.srows = op->bufs.d_srows;
-  A.s_col = op->bufs.d_scol;
-  A.s_val = op->bufs.d_sval;
+// The layout's format fields, the ones variant_of reads (tpl_device.h): set here for the
+// launchers' CsrDev and for tpl_op_kernel_variant alike.
+static void format_fields(const Layout& L, CsrDev& A) {
   A.val_i8 = L.val_i8 ? 1 : 0;
   A.s_col16 = L.s_col16 ? 1 : 0;
   A.b_col16 = L.b_col16 ? 1 : 0;
+  A.s_width = L.s_width;
+  A.s_win = L.s_win;
+}
+
+CsrDev csr_dev(const tpl_op_s* op, bool pass1) {
+  const Layout& L = op->lay;
+  CsrDev A;
+  format_fields(L, A);
+  A.srows = op->bufs.d_srows;
+  A.s_col = op->bufs.d_scol;
+  A.s_val = op->bufs.d_sval;
   A.s_cbase = op->bufs.d_scbase;
   A.b_cbase = op->bufs.d_bcbase;
   A.c_base = op->bufs.d_cbase;
@@ -45,7 +53,6 @@ CsrDev csr_dev(const tpl_op_s* op, bool pass1) {
   A.b_hdr = op->bufs.d_bhdr;
   A.P = op->bufs.d_P;
   A.Pcnt = op->bufs.d_Pcnt;
-  A.s_width = L.s_width;
   A.s_identity = L.s_identity;
   A.n_short = (int32_t)L.srows.size();
   A.n_chunks = (int32_t)L.c_base.size();
@@ -63,7 +70,6 @@ CsrDev csr_dev(const tpl_op_s* op, bool pass1) {
   A.ypart = op->part.hybrid ? op->d_yall + (size_t)op->dist->rank * A.y_ld : nullptr;
   A.nch = op->d_nch;
   A.norm_n = op->part.hybrid && op->dist->rank != 0 ? op->part.ns_local : op->part.n;
-  A.s_win = L.s_win;
   A.s_win_max = L.s_win_max;
   A.n = op->part.n;
   A.E = L.E;
@@ -638,6 +644,17 @@ tpl_status tpl_op_slices(tpl_op_t op, int32_t* slices) {
   return guarded([&] {
     if (!op || !slices) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
     *slices = op->lay.nslices;
+  });
+}
+
+tpl_status tpl_op_kernel_variant(tpl_op_t op, int32_t* variant) {
+  return guarded([&] {
+    if (!op || !variant) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    // what TPL_LAUNCH_CW dispatches on: variant_of over the fields csr_dev gives the
+    // launchers, taken from the layout alone (a host plan has no device view to build)
+    CsrDev A{};
+    format_fields(op->lay, A);
+    *variant = variant_of(A);
   });
 }
 

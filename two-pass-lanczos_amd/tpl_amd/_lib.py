@@ -112,6 +112,7 @@ tpl_op_schedule = _sig("tpl_op_schedule", c_int, c_void_p, POINTER(c_int32), POI
 tpl_op_set_schedule = _sig("tpl_op_set_schedule", c_int, c_void_p, c_int32, c_int32)
 tpl_op_slices = _sig("tpl_op_slices", c_int, c_void_p, POINTER(c_int32))
 tpl_op_set_slices = _sig("tpl_op_set_slices", c_int, c_void_p, c_int32)
+tpl_op_kernel_variant = _sig("tpl_op_kernel_variant", c_int, c_void_p, POINTER(c_int32))
 tpl_profile_kernel = _sig("tpl_profile_kernel", c_int, c_void_p, c_int, c_int, PD, PD)
 tpl_kernel_algo_bytes = _sig("tpl_kernel_algo_bytes", c_double, c_void_p, c_int)
 tpl_copy_to_host = _sig("tpl_copy_to_host", c_int, c_void_p, c_void_p, c_size_t)
@@ -168,7 +169,7 @@ EXPORTED = [
     "tpl_op_device_bytes", "tpl_op_reorth_second_passes", "tpl_op_set_reorder",
     "tpl_op_permutation", "tpl_locality_order", "tpl_op_tune_order",
     "tpl_last_error_detail", "tpl_op_set_order_groups", "tpl_op_order_groups",
-    "tpl_op_ftk_device",
+    "tpl_op_ftk_device", "tpl_op_kernel_variant",
 ]
 
 

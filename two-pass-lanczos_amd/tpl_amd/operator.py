@@ -99,6 +99,7 @@ class HostPlan:
         self.local_rows = rows[:self._n]
 
     schedule = None  # bound below (HipCsrOp.schedule: host reads only)
+    kernel_variant = None  # bound below (HipCsrOp.kernel_variant)
 
     @property
     def handle(self) -> int:
@@ -210,6 +211,13 @@ class HipCsrOp:
                 "G2": g2.value, "E": e.value, "slices": sl.value,
                 "perm": None if ident else perm.copy()}
 
+    def kernel_variant(self) -> int:
+        """The variant flag F of the layout (tpl_op_kernel_variant): the instance of the
+        SpMV-shaped kernels the launchers dispatch to. Host read only."""
+        v = c_int32()
+        check(_lib.tpl_op_kernel_variant(self._op, byref(v)))
+        return int(v.value)
+
     def tune_order(self, groups=None, iters: int = 100):
         """Time the pass-one and pass-two SpMV under each locality-order group count
         (default 12..20, 22, 24) and keep the fastest: -> (groups, microseconds)."""
@@ -318,6 +326,7 @@ class HipCsrOp:
 
 
 HostPlan.schedule = HipCsrOp.schedule
+HostPlan.kernel_variant = HipCsrOp.kernel_variant
 
 
 # -- the caller's own matrix as `operator` (the reference's call sites pass `&a.as_ref()`,
