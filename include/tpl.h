@@ -206,6 +206,29 @@ tpl_status tpl_lanczos(tpl_op_t op, const double* b, int64_t b_len, size_t k,
  * On an error x_out is unspecified.                                               */
 tpl_status tpl_lanczos_two_pass(tpl_op_t op, const double* b, int64_t b_len, size_t k,
                                 tpl_ftk_fn f, void* f_user, double* x_out, int mem);
+/* ---- f_1(A) b ... f_m(A) b over one Krylov space (an extension: the reference's
+ *      f_tk_solver returns a Mat and rejects ncols != 1, src/solvers.rs:78,158) ------
+ * Pass one and the basis pass two regenerates depend on (A, b, k) only; the functions
+ * differ in y = ||b|| f(T_k) e_1 alone. One call runs pass one once, calls fs[0..m) in
+ * index order on the host (each once, with f_users[i] as its `user`; f_users may be NULL),
+ * and runs ONE pass two that regenerates the basis once and accumulates all m results.
+ * x_out is column-major n x m with leading dimension n; column i is bitwise what
+ * tpl_lanczos_two_pass gives for fs[i] with f(T_k) on the host (tpl_op_set_device_ftk 0).
+ * f is always evaluated on the host (tpl_op_flags bit 5 reads 0 afterwards). Errors are
+ * those of the single solve, checked per column, the first failing index reported;
+ * m == 0, m > TPL_MULTI_MAX, NULL fs or x_out: TPL_ERR_INVALID_ARGUMENT; a partitioned
+ * operator: TPL_ERR_UNSUPPORTED. Not supported: v_out, re-orthogonalisation, live timing
+ * (tpl_op_pass_timing keeps the last single solve's values).                          */
+enum { TPL_MULTI_MAX = 64 };
+tpl_status tpl_lanczos_two_pass_multi(tpl_op_t op, const double* b, int64_t b_len, size_t k,
+                                      const tpl_ftk_fn* fs, void** f_users, size_t m,
+                                      double* x_out, int mem);
+/* The one-pass sibling: one standard pass (V_k in HBM), then x_i = ||b|| V_k y'_i per
+ * function; column i is bitwise tpl_lanczos's host-f result for fs[i].                */
+tpl_status tpl_lanczos_multi(tpl_op_t op, const double* b, int64_t b_len, size_t k,
+                             const tpl_ftk_fn* fs, void** f_users, size_t m,
+                             double* x_out, int mem);
+
 /* Where tpl_lanczos_two_pass evaluates the built-in f(T_k): mode 0 = host (two graphs
  * around the host call), 1 = device (the whole solve one graph), 2 = auto (default).
  *   inv: device for k <= 1365 in mode 1, k <= 500 in mode 2: the host solver's exact
@@ -268,6 +291,16 @@ tpl_status tpl_lanczos_pass_two(tpl_op_t op, const double* b, int64_t b_len,
                                 size_t n_betas, size_t steps, double b_norm,
                                 const double* y, size_t y_len, double* x_out,
                                 double* v_out, int mem);
+
+/* lanczos_pass_two for m coefficient vectors over one decomposition: y is column-major
+ * y_len x m (y_len must equal steps: ParameterMismatch `y_k`), x_out column-major n x m
+ * (leading dimension n); the basis is regenerated once. Column i is bitwise
+ * tpl_lanczos_pass_two's x for y's column i. Single-GPU operators; 1 <= m <= TPL_MULTI_MAX. */
+tpl_status tpl_lanczos_pass_two_multi(tpl_op_t op, const double* b, int64_t b_len,
+                                      const double* alphas, size_t n_alphas,
+                                      const double* betas, size_t n_betas, size_t steps,
+                                      double b_norm, const double* y, size_t y_len, size_t m,
+                                      double* x_out, int mem);
 
 /* ---- data loader: src/utils/data_loader.rs:211-259 (load_kkt_system) ----- */
 typedef struct tpl_csr_host {

@@ -3,6 +3,7 @@
  * crate's public surface for this path, so a compiled caller reads like the reference:
  *
  *   tpl::solvers::lanczos / lanczos_two_pass          src/solvers.rs:46-107, 133-175
+ *   tpl::solvers::lanczos_two_pass_multi / lanczos_multi   (none: m functions, one Krylov run)
  *   tpl::algorithms::lanczos_standard                 src/algorithms/lanczos.rs:55-156
  *   tpl::algorithms::lanczos_pass_one                 src/algorithms/lanczos_two_pass.rs:65-110
  *   tpl::algorithms::lanczos_pass_two[_with_basis]    src/algorithms/lanczos_two_pass.rs:128-166
@@ -426,6 +427,64 @@ inline std::vector<double> lanczos_two_pass(const HipCsrOp& op, const std::vecto
   return detail::solve(op, b, k, f_tk_solver,
                        [](tpl_op_t o, const double* bp, int64_t n, size_t kk, tpl_ftk_fn fn, void* u,
                           double* x) { return tpl_lanczos_two_pass(o, bp, n, kk, fn, u, x, TPL_MEM_HOST); });
+}
+}  // namespace solvers
+
+namespace detail {
+// f_1(A) b ... f_m(A) b over one Krylov space (tpl_lanczos_two_pass_multi / tpl_lanczos_multi):
+// every closure runs on the host, in index order; a built-in goes by its own pointer.
+template <class Call>
+Mat solve_multi(const HipCsrOp& op, const std::vector<double>& b, size_t k,
+                const std::vector<FtkSolver>& fs, Call call) {
+  check_b(op, b);
+  const size_t m = fs.size();
+  Mat x(op.nrows(), m);
+  std::vector<FtkCall> calls(m);
+  std::vector<tpl_ftk_fn> fns(m);
+  std::vector<void*> users(m);
+  for (size_t i = 0; i < m; ++i) {
+    calls[i].f = &fs[i];
+    if (is_builtin(fs[i], &fns[i])) {
+      users[i] = nullptr;
+    } else {
+      fns[i] = &ftk_trampoline;
+      users[i] = &calls[i];
+    }
+  }
+  const tpl_status st = call(op.handle(), b.data(), (int64_t)b.size(), k, fns.data(), users.data(),
+                             m, x.data.data());
+  if (st == TPL_ERR_PARAMETER_MISMATCH)
+    for (const FtkCall& c : calls)  // the first failure ends the call: at most one is marked
+      if (c.cols_mismatch) {
+        tpl_error_detail d{};
+        tpl_last_error_detail(&d);
+        throw LanczosError::parameter_mismatch("y_k_prime", (size_t)d.expected, c.rows);
+      }
+  detail::check(st);
+  return x;
+}
+}  // namespace detail
+
+namespace solvers {
+// One two-pass run for m functions: pass one once, every f_i(T_k) e_1 on the host, one pass
+// two that regenerates the basis once. Column i of the n x m result is bitwise
+// lanczos_two_pass's with f_tk_solvers[i] evaluated on the host.
+inline Mat lanczos_two_pass_multi(const HipCsrOp& op, const std::vector<double>& b, size_t k,
+                                  const std::vector<FtkSolver>& f_tk_solvers) {
+  return detail::solve_multi(op, b, k, f_tk_solvers,
+                             [](tpl_op_t o, const double* bp, int64_t n, size_t kk, const tpl_ftk_fn* fn,
+                                void** u, size_t m, double* x) {
+                               return tpl_lanczos_two_pass_multi(o, bp, n, kk, fn, u, m, x, TPL_MEM_HOST);
+                             });
+}
+// The one-pass sibling: one standard pass, then x_i = ||b|| V_k y'_i per function.
+inline Mat lanczos_multi(const HipCsrOp& op, const std::vector<double>& b, size_t k,
+                         const std::vector<FtkSolver>& f_tk_solvers) {
+  return detail::solve_multi(op, b, k, f_tk_solvers,
+                             [](tpl_op_t o, const double* bp, int64_t n, size_t kk, const tpl_ftk_fn* fn,
+                                void** u, size_t m, double* x) {
+                               return tpl_lanczos_multi(o, bp, n, kk, fn, u, m, x, TPL_MEM_HOST);
+                             });
 }
 }  // namespace solvers
 

@@ -122,6 +122,16 @@ extern "C" {
                             n_alphas: usize, betas: *const f64, n_betas: usize, steps: usize,
                             b_norm: f64, y: *const f64, y_len: usize, x_out: *mut f64,
                             v_out: *mut f64, mem: c_int) -> c_int;
+    fn tpl_lanczos_two_pass_multi(op: *mut TplOp, b: *const f64, b_len: i64, k: usize,
+                                  fs: *const FtkFn, f_users: *mut *mut c_void, m: usize,
+                                  x_out: *mut f64, mem: c_int) -> c_int;
+    fn tpl_lanczos_multi(op: *mut TplOp, b: *const f64, b_len: i64, k: usize,
+                         fs: *const FtkFn, f_users: *mut *mut c_void, m: usize,
+                         x_out: *mut f64, mem: c_int) -> c_int;
+    fn tpl_lanczos_pass_two_multi(op: *mut TplOp, b: *const f64, b_len: i64,
+                                  alphas: *const f64, n_alphas: usize, betas: *const f64,
+                                  n_betas: usize, steps: usize, b_norm: f64, y: *const f64,
+                                  y_len: usize, m: usize, x_out: *mut f64, mem: c_int) -> c_int;
     fn tpl_copy_to_host(dst: *mut c_void, src_device: *const c_void, bytes: usize) -> c_int;
     fn tpl_op_nrows(op: *mut TplOp) -> i64;
     fn tpl_op_local_rows(op: *mut TplOp, rows: *mut i64) -> c_int;
@@ -731,5 +741,94 @@ pub fn lanczos_pass_two_with_basis(
     operator.with_hip_op(|op| {
         pass_two(op, b, decomposition, y_k, true)
             .map(|(x_k, v_k)| LanczosPassTwoOutput { x_k, v_k: v_k.unwrap() })
+    })?
+}
+
+/// The two multi-function solves: `call` is tpl_lanczos_two_pass_multi or tpl_lanczos_multi.
+type MultiFn = unsafe extern "C" fn(*mut TplOp, *const f64, i64, usize, *const FtkFn,
+                                    *mut *mut c_void, usize, *mut f64, c_int) -> c_int;
+
+fn solve_multi<O, F>(operator: &O, b: MatRef<'_, f64>, k: usize, f_tk_solvers: &mut [F],
+                     call: MultiFn) -> Result<Mat<f64>, LanczosError>
+where
+    O: HipOperand,
+    F: FnMut(&[f64], &[f64]) -> Result<Mat<f64>, anyhow::Error>,
+{
+    let bv = column(b);
+    let m = f_tk_solvers.len();
+    let fns: Vec<FtkFn> = vec![ftk_trampoline::<F> as FtkFn; m];
+    let mut users: Vec<*mut c_void> =
+        f_tk_solvers.iter_mut().map(|f| f as *mut F as *mut c_void).collect();
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n * m];
+        let _g = op.lock.lock().unwrap();
+        unsafe {
+            check(call(op.op, bv.as_ptr(), bv.len() as i64, k, fns.as_ptr(), users.as_mut_ptr(),
+                       m, x.as_mut_ptr(), TPL_MEM_HOST))?;
+        }
+        Ok(column_major(&x, op.n, m))
+    })?
+}
+
+/// f_1(A) b ... f_m(A) b by ONE two-pass run (no reference counterpart: its `f_tk_solver`
+/// returns a `Mat` and rejects ncols != 1): pass one once, every closure once in index
+/// order, one pass two. Column i is bitwise `lanczos_two_pass` with `f_tk_solvers[i]`.
+pub fn lanczos_two_pass_multi<O, F>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    k: usize,
+    stack: &mut MemStack,
+    f_tk_solvers: &mut [F],
+) -> Result<Mat<f64>, LanczosError>
+where
+    O: HipOperand,
+    F: FnMut(&[f64], &[f64]) -> Result<Mat<f64>, anyhow::Error>,
+{
+    let _ = stack;
+    solve_multi(operator, b, k, f_tk_solvers, tpl_lanczos_two_pass_multi)
+}
+
+/// The one-pass sibling of `lanczos_two_pass_multi`: one standard pass, one reconstruction
+/// per function.
+pub fn lanczos_multi<O, F>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    k: usize,
+    stack: &mut MemStack,
+    f_tk_solvers: &mut [F],
+) -> Result<Mat<f64>, LanczosError>
+where
+    O: HipOperand,
+    F: FnMut(&[f64], &[f64]) -> Result<Mat<f64>, anyhow::Error>,
+{
+    let _ = stack;
+    solve_multi(operator, b, k, f_tk_solvers, tpl_lanczos_multi)
+}
+
+/// `lanczos_pass_two` for the m columns of `y_k` (steps x m) over one decomposition: the
+/// basis is regenerated once; returns n x m.
+pub fn lanczos_pass_two_multi(
+    operator: &impl HipOperand,
+    b: MatRef<'_, f64>,
+    decomposition: &LanczosDecomposition<f64>,
+    y_k: MatRef<'_, f64>,
+    stack: &mut MemStack,
+) -> Result<Mat<f64>, LanczosError> {
+    let _ = stack;
+    let bv = column(b);
+    let (rows, m) = (y_k.nrows(), y_k.ncols());
+    let yv: Vec<f64> = (0..rows * m).map(|t| y_k[(t % rows, t / rows)]).collect();
+    let d = decomposition;
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n * m];
+        let _g = op.lock.lock().unwrap();
+        unsafe {
+            check(tpl_lanczos_pass_two_multi(op.op, bv.as_ptr(), bv.len() as i64,
+                                             d.alphas.as_ptr(), d.alphas.len(),
+                                             d.betas.as_ptr(), d.betas.len(), d.steps_taken,
+                                             d.b_norm, yv.as_ptr(), rows, m, x.as_mut_ptr(),
+                                             TPL_MEM_HOST))?;
+        }
+        Ok(column_major(&x, op.n, m))
     })?
 }

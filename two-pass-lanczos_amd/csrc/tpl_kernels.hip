@@ -11,6 +11,8 @@
 //   tpl_k_p1_gp.hip     k_p1_spmv_gp   } the pass-one SpMV for gathered / for more than 256
 //   tpl_k_p1_wide.hip   k_p1_spmv_wide } norm partials: partitioned and very large operators
 //   tpl_k_ftk_exp.hip   k_ftk_exp
+//   tpl_k_multi.hip     k_p2_minit, k_p2_xacc (multi-function pass two: the x updates of
+//                       every column, with k_p2_spmv run at nflush = 0)
 //   tpl_k_dist_reorth.hip  k_long_epi_p1 / _y / _p2 (partitioned solve) and k_reorth_dot /
 //                       _reduce / _update / _decide: one unit, see its header
 //   tpl_kcommon.h       device building blocks: reductions, epilogues, the sliced-ELL chunk,

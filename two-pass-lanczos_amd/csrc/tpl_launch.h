@@ -32,6 +32,15 @@ hipError_t p2_spmv(const CsrDev& A, const DevState& S, const double* xsrc, const
 hipError_t p2_coefs(const DevState& S, int k, int dyn, hipStream_t s);
 hipError_t gemv_recon(int64_t n, int steps, const DevState& S, const double* V, double* x,
                       hipStream_t s);
+// multi-function pass two (tpl_k_multi.hip). Y: the coefficient table, column i at
+// Y + i * ldy; X: the m result vectors, column i at X + i * ldx.
+// p2_minit: v_1 = b / ||b||, X_i = v_1 y_i[0]. p2_xacc: after step j, the last nflush
+// (1..3) x terms of m <= 8 columns from vp / vc / vn = v_{j-1}, v_j, v_{j+1}.
+hipError_t p2_minit(const CsrDev& A, const DevState& S, const double* Y, int ldy, const double* b,
+                    double* v1, double* X, int64_t ldx, int m, hipStream_t s);
+hipError_t p2_xacc(const CsrDev& A, const double* Y, int ldy, int j, int nflush, const double* vp,
+                   const double* vc, const double* vn, double* X, int64_t ldx, int m,
+                   hipStream_t s);
 int long_epi_blocks(const CsrDev& A);  // workgroups over the long rows (kLongEpiRows each)
 hipError_t long_epi_p1(const CsrDev& A, const DevState& S, const double* yall, int R,
                        const double* r_cur, const double* r_prev, double* W, double* Vcol,

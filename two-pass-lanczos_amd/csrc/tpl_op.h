@@ -140,6 +140,10 @@ struct tpl_op_s {
   tpl::SolverState st;
   double* d_V = nullptr;    // standard-variant basis (n x vcols, ld = n); nullptr: vcols == 0
   size_t vcols = 0;
+  // multi-function solves (ensure_multi): the result vectors X (xcols columns, ldx = ld
+  // apart) and the coefficient table Y (xcols columns, ycap apart); nullptr: xcols == 0
+  double *d_X = nullptr, *d_Y = nullptr;
+  size_t xcols = 0, ycap = 0;
   std::map<std::pair<int, size_t>, tpl::GraphExec> graphs;
   // device allocations of this operator (pointer -> bytes): tpl_op_device_bytes
   std::map<const void*, size_t> allocs;
@@ -198,6 +202,10 @@ uint64_t device_bytes(const tpl_op_s* op);
 void rebuild_schedule(tpl_op_s* op, const SchedParams& cand, int reorder);
 void ensure_state(tpl_op_s* op, size_t k, bool reorth = false);
 void ensure_basis(tpl_op_s* op, size_t cols);
+// The m result vectors and the m x kcap coefficient table of a multi-function solve, for
+// the state's current kcap (ensure_state first). They grow with m and kcap; growing drops
+// the cached graphs.
+void ensure_multi(tpl_op_s* op, size_t m);
 double* ensure_view(tpl_op_s* op, size_t cols);
 // Per-step second-pass records of the selective re-orthogonalisation (slot j - 1: step j).
 int* reorth_records(const tpl_op_s* op);
@@ -206,6 +214,10 @@ inline void sync_checked(tpl_op_s* op) { HIPCHK(hipStreamSynchronize(op->stream)
 void check_b(const tpl_op_s* op, const double* b, int64_t b_len);
 void upload_vec(tpl_op_s* op, double* dst, const double* src, int mem);
 void download_vec(tpl_op_s* op, double* dst, const double* src, int64_t cols, int mem);
+// `cols` device vectors `lds` apart (internal order) out to the caller's n x cols matrix
+// (ld = n, the caller's order), a column at a time.
+void download_cols(tpl_op_s* op, double* dst, const double* src, int64_t lds, int64_t cols,
+                   int mem);
 void set_stride(tpl_op_s* op);
 std::unique_ptr<tpl_op_s> make_op(tpl_ctx_s* ctx, tpl_dist_s* dist, RankPlan&& part);
 void init_op(tpl_op_s* op);
@@ -251,6 +263,9 @@ void enqueue_ftk_only(tpl_op_s* op, size_t k, int f, int scale);
 void run_pass_one(tpl_op_s* op, const double* b, size_t k, int mem, bool storeV, int reorth,
                   bool elim = false);
 void run_pass2(tpl_op_s* op, size_t steps);
+// Pass two for the m coefficient columns of op->d_Y into op->d_X (ensure_multi): one graph
+// per (steps, m).
+void run_pass2_multi(tpl_op_s* op, size_t steps, size_t m);
 void run_two_pass_dev(tpl_op_s* op, size_t k, int f);
 HostDecomp fetch_decomp(tpl_op_s* op);
 

@@ -323,6 +323,20 @@ void ensure_basis(tpl_op_s* op, size_t cols) {
   dev_alloc(op, &op->d_V, (size_t)op->part.n * c * sizeof(double) + 64);
   op->vcols = c;
 }
+// Freed before they grow, as the basis is.
+void ensure_multi(tpl_op_s* op, size_t m) {
+  const size_t kc = op->st.kcap;
+  if (m <= op->xcols && kc <= op->ycap && op->d_X) return;
+  const size_t cols = std::max(m, op->xcols), cap = std::max(kc, op->ycap);
+  drop_graphs(op);
+  dev_free(op, op->d_X);
+  dev_free(op, op->d_Y);
+  op->xcols = op->ycap = 0;
+  dev_alloc(op, &op->d_X, cols * (size_t)op->ld * sizeof(double));
+  dev_alloc(op, &op->d_Y, cols * cap * sizeof(double));
+  op->xcols = cols;
+  op->ycap = cap;
+}
 // The step callback's view of V_k in the caller's row order: the basis itself, or (a
 // reordered operator) an n x cols buffer each batch's new columns are gathered into.
 double* ensure_view(tpl_op_s* op, size_t cols) {
@@ -393,6 +407,12 @@ void download_vec(tpl_op_s* op, double* dst, const double* src, int64_t cols, in
     HIPCHK(hipMemcpyAsync(dst + c * n, op->bufs.d_stage, n * sizeof(double),
                           hipMemcpyDeviceToHost, op->stream));
   }
+}
+
+void download_cols(tpl_op_s* op, double* dst, const double* src, int64_t lds, int64_t cols,
+                   int mem) {
+  for (int64_t c = 0; c < cols; ++c)
+    download_vec(op, dst + c * op->part.n, src + c * lds, 1, mem);
 }
 
 // Vector stride ld, common to all ranks (the gathered vector holds rank r's block at r * ld).

@@ -19,6 +19,7 @@ enum GraphKind {
   kGTwoPassDev,       // one-graph solve: pass one, device f(T_k), pass two
   kGDevFtk,           // (timed variant) device f(T_k) + pass-two prologue
   kGPass2Dyn,         // (timed variant) the k - 1 step launches of a one-graph solve
+  kGPass2Multi,       // pass two of a multi-function solve: one graph per (steps, m)
 };
 // What tells one pass-one sequence (and its graph) from another, beside k: the basis is
 // stored (the standard pass), T_k's LU is eliminated as it goes (a device inv follows:
@@ -242,6 +243,36 @@ void run_pass2(tpl_op_s* op, size_t steps) {
   run_graph(op, kGPass2Steps, steps, [&] { enqueue_pass2_steps(op, steps, nullptr); });
   HIPCHK(hipEventRecord(op->tev[3], op->stream));
   op->p2_launches = (int64_t)steps - 1;
+}
+
+// Pass two for m functions over one Krylov space (tpl_lanczos_two_pass_multi): the basis
+// is regenerated once — every step launch runs with nflush = 0, so k_p2_spmv writes
+// v_{j+1} and leaves x alone — and after each step of the single solve's flush schedule
+// (p2_flush) k_p2_xacc applies that step's grouped flush to every column, up to 8 columns
+// per launch, from the three live ring vectors: column i gets the single solve's bits.
+static void enqueue_pass2_multi(tpl_op_s* op, size_t steps, size_t m) {
+  const CsrDev A = csr_dev(op);
+  const int ldy = (int)op->ycap;
+  HIPCHK(launch::p2_minit(A, op->st.S, op->d_Y, ldy, op->b, op->V2[1], op->d_X, op->ld, (int)m,
+                          op->stream));
+  HIPCHK(launch::p2_coefs(op->st.S, (int)steps, 0, op->stream));
+  for (int j = 1; j < (int)steps; ++j) {
+    launch_p2_step(op, A, j, j, 0, nullptr);
+    const int nflush = p2_flush(j, (int)steps - 1);
+    if (!nflush) continue;
+    const P2Rot v = p2_rot(op, j);
+    for (size_t c0 = 0; c0 < m; c0 += 8)
+      HIPCHK(launch::p2_xacc(A, op->d_Y + c0 * op->ycap, ldy, j, nflush, v.prev, v.cur, v.next,
+                             op->d_X + c0 * (size_t)op->ld, op->ld, (int)std::min<size_t>(8, m - c0),
+                             op->stream));
+  }
+}
+void run_pass2_multi(tpl_op_s* op, size_t steps, size_t m) {
+  if (op->dist) fail(TPL_ERR_UNSUPPORTED, "multi-function solve of a partitioned operator");
+  if (m == 0 || m > op->xcols || steps > op->ycap || m > TPL_MULTI_MAX)
+    fail(TPL_ERR_INVALID_ARGUMENT, "run_pass2_multi: buffers smaller than the request");
+  run_graph(op, kGPass2Multi, steps * (TPL_MULTI_MAX + 1) + m,
+            [&] { enqueue_pass2_multi(op, steps, m); });
 }
 
 // Copy flags | norms[0] | alphas | betas back (one D2H), synchronise.

@@ -345,6 +345,142 @@ tpl_status tpl_lanczos(tpl_op_t op, const double* b, int64_t b_len, size_t k, tp
   });
 }
 
+} // extern "C"
+
+// ---- f_1(A) b ... f_m(A) b over one Krylov space ------------------------------------
+namespace {
+// What every multi entry point checks first; leaves the operator's device current.
+void check_multi(tpl_op_s* op, bool have_args, size_t m) {
+  if (!op || !have_args) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (m == 0 || m > (size_t)TPL_MULTI_MAX)
+    fail(TPL_ERR_INVALID_ARGUMENT, "m must be between 1 and TPL_MULTI_MAX");
+  set_device(op);
+  if (op->dist) fail(TPL_ERR_UNSUPPORTED, "multi-function solve of a partitioned operator");
+}
+// The multi solves record no live timing: tpl_op_pass_timing keeps the last single
+// solve's events.
+struct TimingOff {
+  tpl_op_s* op;
+  bool was;
+  explicit TimingOff(tpl_op_s* o) : op(o), was(o->timing) { op->timing = false; }
+  ~TimingOff() { op->timing = was; }
+};
+void zero_out_cols(tpl_op_s* op, double* x_out, size_t m, int mem) {
+  for (size_t i = 0; i < m; ++i) zero_out(op, x_out + i * (size_t)op->part.n, mem);
+}
+// y'_i = f_i(T_k) e_1 for every function, in index order (the first failure throws),
+// times ||b|| when `scale`: steps x m, column-major.
+std::vector<double> call_ftks(const tpl_ftk_fn* fs, void** f_users, size_t m,
+                              const HostDecomp& d, bool scale) {
+  std::vector<double> Y(m * d.steps), y;
+  for (size_t i = 0; i < m; ++i) {
+    call_ftk(fs[i], f_users ? f_users[i] : nullptr, d, y);
+    for (size_t j = 0; j < d.steps; ++j) Y[i * d.steps + j] = scale ? y[j] * d.b_norm : y[j];
+  }
+  return Y;
+}
+// The steps x m host table into the device table (columns ycap apart).
+void upload_y(tpl_op_s* op, const double* Y, size_t steps, size_t m) {
+  HIPCHK(hipMemcpy2DAsync(op->d_Y, op->ycap * sizeof(double), Y, steps * sizeof(double),
+                          steps * sizeof(double), m, hipMemcpyHostToDevice, op->stream));
+}
+} // namespace
+
+extern "C" {
+
+tpl_status tpl_lanczos_two_pass_multi(tpl_op_t op, const double* b, int64_t b_len, size_t k,
+                                      const tpl_ftk_fn* fs, void** f_users, size_t m,
+                                      double* x_out, int mem) {
+  return guarded([&] {
+    check_multi(op, fs && x_out, m);
+    check_b(op, b, b_len);
+    check_k(k);
+    const TimingOff untimed(op);
+    // 1. pass one, once (the host-f path of tpl_lanczos_two_pass)
+    op->last_one_graph = false;
+    run_pass_one(op, b, k, mem, false, false);
+    const HostDecomp d = fetch_decomp(op);
+    if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+    if (d.steps == 0) {
+      zero_out_cols(op, x_out, m, mem);
+      return;
+    }
+    // 2. every f_i(T_k) e_1 on the host, 3. y_i = y'_i * ||b||
+    const std::vector<double> Y = call_ftks(fs, f_users, m, d, true);
+    ensure_multi(op, m);
+    upload_y(op, Y.data(), d.steps, m);
+    // 4. one pass two for all of them
+    run_pass2_multi(op, d.steps, m);
+    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+    sync_checked(op);
+  });
+}
+
+tpl_status tpl_lanczos_multi(tpl_op_t op, const double* b, int64_t b_len, size_t k,
+                             const tpl_ftk_fn* fs, void** f_users, size_t m, double* x_out,
+                             int mem) {
+  return guarded([&] {
+    check_multi(op, fs && x_out, m);
+    check_b(op, b, b_len);
+    check_k(k);
+    const TimingOff untimed(op);
+    op->last_one_graph = false;
+    run_pass_one(op, b, k, mem, true, false);
+    const HostDecomp d = fetch_decomp(op);
+    if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+    if (d.steps == 0) {
+      zero_out_cols(op, x_out, m, mem);
+      return;
+    }
+    const std::vector<double> Y = call_ftks(fs, f_users, m, d, false);
+    ensure_multi(op, m);
+    // x_i = ||b|| V_k y'_i: the single solve's reconstruction, a column at a time
+    for (size_t i = 0; i < m; ++i) {
+      HIPCHK(hipMemcpyAsync(op->st.S.y, Y.data() + i * d.steps, d.steps * sizeof(double),
+                            hipMemcpyHostToDevice, op->stream));
+      HIPCHK(launch::gemv_recon(op->part.n, (int)d.steps, op->st.S, op->d_V,
+                                op->d_X + i * (size_t)op->ld, op->stream));
+    }
+    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+    sync_checked(op);
+  });
+}
+
+tpl_status tpl_lanczos_pass_two_multi(tpl_op_t op, const double* b, int64_t b_len,
+                                      const double* alphas, size_t n_alphas,
+                                      const double* betas, size_t n_betas, size_t steps,
+                                      double b_norm, const double* y, size_t y_len, size_t m,
+                                      double* x_out, int mem) {
+  return guarded([&] {
+    check_multi(op, x_out != nullptr, m);  // y may be NULL with steps == 0
+    check_b(op, b, b_len);
+    if (steps != y_len) fail_param_mismatch("y_k", steps, y_len);
+    if (b_norm <= kBreakdownTol)
+      fail_input("The initial vector `b` must not be a zero vector.");
+    if (steps == 0) {
+      zero_out_cols(op, x_out, m, mem);
+      return;
+    }
+    if (n_alphas < steps || n_betas + 1 < steps || !alphas || (steps > 1 && !betas) || !y)
+      fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
+    if (steps > (size_t)INT32_MAX / 2) fail(TPL_ERR_INVALID_ARGUMENT, "steps too large");
+    ensure_state(op, steps);
+    ensure_multi(op, m);
+    const DevState& S = op->st.S;
+    HIPCHK(hipMemcpyAsync(S.norms, &b_norm, sizeof(double), hipMemcpyHostToDevice, op->stream));
+    HIPCHK(hipMemcpyAsync(S.alphas, alphas, steps * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    if (steps > 1)
+      HIPCHK(hipMemcpyAsync(S.betas, betas, (steps - 1) * sizeof(double), hipMemcpyHostToDevice,
+                            op->stream));
+    upload_y(op, y, steps, m);
+    upload_vec(op, op->b, b, mem);
+    run_pass2_multi(op, steps, m);
+    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+    sync_checked(op);
+  });
+}
+
 tpl_status tpl_op_reorth_second_passes(tpl_op_t op, int64_t* count) {
   return guarded([&] {
     if (!op || !count) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");

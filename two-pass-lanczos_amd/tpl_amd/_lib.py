@@ -103,6 +103,15 @@ tpl_lanczos_pass_one = _sig("tpl_lanczos_pass_one", c_int, c_void_p, c_void_p, c
 tpl_lanczos_pass_two = _sig("tpl_lanczos_pass_two", c_int, c_void_p, c_void_p, c_int64, PD,
                             c_size_t, PD, c_size_t, c_size_t, c_double, PD, c_size_t, c_void_p,
                             c_void_p, c_int)
+TPL_MULTI_MAX = 64
+tpl_lanczos_two_pass_multi = _sig("tpl_lanczos_two_pass_multi", c_int, c_void_p, c_void_p, c_int64,
+                                  c_size_t, POINTER(c_void_p), POINTER(c_void_p), c_size_t,
+                                  c_void_p, c_int)
+tpl_lanczos_multi = _sig("tpl_lanczos_multi", c_int, c_void_p, c_void_p, c_int64, c_size_t,
+                         POINTER(c_void_p), POINTER(c_void_p), c_size_t, c_void_p, c_int)
+tpl_lanczos_pass_two_multi = _sig("tpl_lanczos_pass_two_multi", c_int, c_void_p, c_void_p, c_int64,
+                                  PD, c_size_t, PD, c_size_t, c_size_t, c_double, PD, c_size_t,
+                                  c_size_t, c_void_p, c_int)
 tpl_load_kkt_system = _sig("tpl_load_kkt_system", c_int, c_char_p, c_char_p, POINTER(CsrHost))
 tpl_csr_host_free = _sig("tpl_csr_host_free", None, POINTER(CsrHost))
 tpl_generate_kkt = _sig("tpl_generate_kkt", c_int, c_int64, c_int64, ctypes.c_uint64,
@@ -219,6 +228,7 @@ TPL_PLAN_SINGLE, TPL_PLAN_REPLICATED, TPL_PLAN_ROWS, TPL_PLAN_HALO = 0, 1, 2, 3
 tpl_plan_create = _sig("tpl_plan_create", c_int, c_int64, POINTER(c_int64), POINTER(c_int32), PD,
                        c_int, c_int, c_int, c_int32, POINTER(c_void_p))
 EXPORTED += ["tpl_plan_create"]
+EXPORTED += ["tpl_lanczos_two_pass_multi", "tpl_lanczos_multi", "tpl_lanczos_pass_two_multi"]
 EXPORTED += ["tpl_dist_op_create_replicated", "tpl_op_local_rows", "tpl_dist_partition", "tpl_dist_unique_id", "tpl_dist_create",
              "tpl_dist_create_host", "tpl_dist_destroy", "tpl_dist_op_create_csr",
              "tpl_dist_op_create_halo", "tpl_dist_choose_partition", "tpl_dist_op_create_auto",

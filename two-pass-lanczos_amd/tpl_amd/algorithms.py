@@ -11,6 +11,7 @@ this module                            reference
 ``lanczos_pass_one``                   src/algorithms/lanczos_two_pass.rs:65-110
 ``lanczos_pass_two``                   src/algorithms/lanczos_two_pass.rs:128-140
 ``lanczos_pass_two_with_basis``        src/algorithms/lanczos_two_pass.rs:149-166
+``lanczos_pass_two_multi``             (none: pass two for m coefficient vectors at once)
 =====================================  ================================================
 
 Every call runs the recurrence on the GPU through libtpl_amd.so (C ABI,
@@ -180,3 +181,27 @@ def lanczos_pass_two_with_basis(operator, b, decomposition: LanczosDecomposition
     src/algorithms/lanczos_two_pass.rs:149-166."""
     x, v = _pass_two(operator, b, decomposition, y_k, True)
     return LanczosPassTwoOutput(x, v)
+
+
+def lanczos_pass_two_multi(operator, b, decomposition: LanczosDecomposition, Y):
+    """Second pass for m coefficient vectors over one decomposition: ``Y`` is (steps, m),
+    column i = f_i(T_k) e_1 * ||b||. The basis is regenerated once. Returns shape (n, m)
+    with strides (1, n); column i is bitwise ``lanczos_pass_two`` with ``Y[:, i]``."""
+    y = Y.detach().double().cpu().numpy() if hasattr(Y, "is_cuda") else np.asarray(Y, dtype=np.float64)
+    if y.ndim != 2:
+        raise ValueError("Y must be a (steps, m) matrix")
+    y_len, m = y.shape
+    if m == 0:
+        raise ValueError("Y must hold at least one column")
+    op = _op(operator)
+    bv = Vec(b)
+    yt = np.ascontiguousarray(y.T)  # C-order (m, y_len) == column-major (y_len, m)
+    a = np.ascontiguousarray(decomposition.alphas, dtype=np.float64).reshape(-1)
+    bb = np.ascontiguousarray(decomposition.betas, dtype=np.float64).reshape(-1)
+    x = bv.empty(m, op.nrows())
+    check(_lib.tpl_lanczos_pass_two_multi(
+        op.handle, bv.ptr, bv.n, a.ctypes.data_as(POINTER(c_double)), a.shape[0],
+        bb.ctypes.data_as(POINTER(c_double)), bb.shape[0], int(decomposition.steps_taken),
+        float(decomposition.b_norm), yt.ctypes.data_as(POINTER(c_double)), y_len, m,
+        Vec.ptr_of(x), bv.mem))
+    return x.T

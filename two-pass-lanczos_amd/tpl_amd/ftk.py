@@ -9,6 +9,10 @@ inside libtpl_amd.so (no Python on the solve path):
   (src/bin/tradeoff.rs:245-258, tests/correctness.rs:171-179)
 * ``EXP`` — Q exp(Lambda) Q^T e_1 by symmetric tridiagonal QL (src/bin/stability.rs:175-193)
 * ``SQ``  — T_k^2 e_1 (tests/correctness.rs:287-299)
+
+Two families over the built-ins, for several functions over one Krylov space
+(``solvers.lanczos_two_pass_multi``): ``exp_t(t)`` — exp(t T_k) e_1 — and
+``inv_shift(sigma)`` — (T_k + sigma I)^{-1} e_1.
 """
 from __future__ import annotations
 
@@ -51,6 +55,27 @@ EXP = BuiltinFtk("EXP", _lib.FTK_EXP_PTR, _lib.tpl_ftk_exp)
 SQ = BuiltinFtk("SQ", _lib.FTK_SQ_PTR, _lib.tpl_ftk_sq)
 
 BUILTINS = {"inv": INV, "exp": EXP, "sq": SQ}
+
+
+def exp_t(t: float):
+    """exp(t T_k) e_1 — exp(tA) b at time t: the native EXP on the scaled T_k."""
+    t = float(t)
+
+    def f(alphas, betas):
+        return EXP(t * np.asarray(alphas, dtype=np.float64),
+                   t * np.asarray(betas, dtype=np.float64))
+    f.__name__ = f"exp_t({t!r})"
+    return f
+
+
+def inv_shift(sigma: float):
+    """(T_k + sigma I)^{-1} e_1 — (A + sigma I)^{-1} b: the native INV on the shifted T_k."""
+    sigma = float(sigma)
+
+    def f(alphas, betas):
+        return INV(np.asarray(alphas, dtype=np.float64) + sigma, betas)
+    f.__name__ = f"inv_shift({sigma!r})"
+    return f
 
 
 class _PyFtk:

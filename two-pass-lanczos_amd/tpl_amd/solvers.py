@@ -10,8 +10,15 @@ matrix (uploaded on first use and re-used while unchanged: ``operator.as_operato
 ``f_tk_solver`` is a callable ``(alphas, betas) -> y'`` or a built-in
 from :mod:`tpl_amd.ftk` (``"inv"``, ``"exp"``, ``"sq"``). Returns x_k with the
 shape of ``b`` flattened to (n,) — numpy for host ``b``, torch CUDA for device ``b``.
+
+``lanczos_two_pass_multi(operator, b, k, f_tk_solvers)`` and ``lanczos_multi`` (no reference
+counterpart) solve f_1(A) b ... f_m(A) b over one Krylov space: one pass one, every f_i on
+the host, one pass two. They return shape (n, m) with strides (1, n) — column i is bitwise
+the single solve with ``f_tk_solvers[i]`` evaluated on the host.
 """
 from __future__ import annotations
+
+import ctypes
 
 from . import _lib, ftk
 from ._vec import Vec
@@ -39,3 +46,36 @@ def lanczos(operator, b, k: int, f_tk_solver):
 def lanczos_two_pass(operator, b, k: int, f_tk_solver):
     """f(A) b by two-pass Lanczos: O(n) memory, the basis is regenerated in pass two."""
     return _run(_lib.tpl_lanczos_two_pass, operator, b, k, f_tk_solver)
+
+
+def _run_multi(fn, operator, b, k, f_tk_solvers):
+    fs = list(f_tk_solvers)
+    if not fs:
+        raise ValueError("f_tk_solvers must hold at least one solver")
+    operator = as_operator(operator)
+    bv = Vec(b)
+    m = len(fs)
+    x = bv.empty(m, operator.nrows())  # C-order (m, n) == column-major (n, m)
+    resolved = [ftk.resolve(f) for f in fs]
+    fptrs = (ctypes.c_void_p * m)(*[p for p, _ in resolved])
+    try:
+        check(fn(operator.handle, bv.ptr, bv.n, k, fptrs, None, m, Vec.ptr_of(x), bv.mem))
+    except LanczosError as e:
+        # the functions run in index order and the first failure ends the call: a solver
+        # that recorded a column-count mismatch is the one that failed
+        for _, keep in resolved:
+            if keep is not None and keep.mismatch is not None:
+                raise ftk.remap_error(e, keep) from None
+        raise
+    return x.T
+
+
+def lanczos_multi(operator, b, k: int, f_tk_solvers):
+    """f_i(A) b, i = 0 .. m-1, by ONE standard pass: column i = ``lanczos`` with f_i."""
+    return _run_multi(_lib.tpl_lanczos_multi, operator, b, k, f_tk_solvers)
+
+
+def lanczos_two_pass_multi(operator, b, k: int, f_tk_solvers):
+    """f_i(A) b, i = 0 .. m-1, by ONE two-pass run: pass one once, every f_i(T_k) on the
+    host, one pass two that regenerates the basis once for all m results."""
+    return _run_multi(_lib.tpl_lanczos_two_pass_multi, operator, b, k, f_tk_solvers)
