@@ -228,6 +228,49 @@ tpl_status tpl_lanczos_two_pass_multi(tpl_op_t op, const double* b, int64_t b_le
 tpl_status tpl_lanczos_multi(tpl_op_t op, const double* b, int64_t b_len, size_t k,
                              const tpl_ftk_fn* fs, void** f_users, size_t m,
                              double* x_out, int mem);
+/* ---- f(A) b_1 ... f(A) b_s in one lock-step run (an extension: the reference's
+ *      solvers::lanczos_two_pass takes one b) -----------------------------------------
+ * The other axis: one f, s right-hand sides. Every b_c has its own Krylov space, its own
+ * alpha, beta, y and breakdown step; the s recurrences share the matrix bytes, every
+ * launch and the address arithmetic of every gather. b_len is n, as elsewhere; B and x_out
+ * are column-major n x s with leading dimension n (host or device, by `mem`).
+ * tpl_lanczos_two_pass_batch runs pass one for all columns in lock-step, then calls f on
+ * the host once per column, in column order, with that column's steps_c alphas and
+ * steps_c - 1 betas, scales by ||b_c|| and runs ONE pass two for all columns. Column c of
+ * x_out is bitwise what tpl_lanczos_two_pass(op, b_c, k, f) returns with f(T_k) on the host
+ * (tpl_op_set_device_ftk(op, 0)); the pass_one_batch outputs of column c are bitwise
+ * tpl_lanczos_pass_one's, pass_two_batch's x of column c is bitwise tpl_lanczos_pass_two's.
+ * Columns are independent: column c's bits do not depend on s, on its position, or on what
+ * the other columns hold, non-finite values included. A column that breaks down at step
+ * j_c keeps steps_c = j_c and its truncated result, as in the single solve; the others run
+ * on to their own end.
+ * Grouping: the columns are taken in order, four per group while four remain, then two
+ * per group; a last single column runs the single host-f solve (so a remainder of three is
+ * a group of two and a single solve: no group is padded). The groups run one after the
+ * other.
+ * f is always evaluated on the host (tpl_op_flags bit 5 reads 0 afterwards). Errors are
+ * those of the single solve, checked per column in ascending order: the first failing
+ * column's error is reported, with the same message text (a zero column: the single
+ * solve's zero-vector InputError). On an error x_out is unspecified. s == 0,
+ * s > TPL_BATCH_MAX, NULL B / x_out / f: TPL_ERR_INVALID_ARGUMENT; a partitioned operator:
+ * TPL_ERR_UNSUPPORTED. Not supported: v_out, re-orthogonalisation, live timing, device
+ * f(T_k) (tpl_op_pass_timing keeps the last single solve's values).                    */
+enum { TPL_BATCH_MAX = 64 };
+/* B, x_out: column-major n x s, leading dimension n (host or device, by `mem`). */
+tpl_status tpl_lanczos_two_pass_batch(tpl_op_t op, const double* B, int64_t b_len, size_t s,
+                                      size_t k, tpl_ftk_fn f, void* f_user,
+                                      double* x_out, int mem);
+/* alphas, betas: column-major k x s (ld = k; betas uses k-1 per column);
+ * steps, b_norms: s entries */
+tpl_status tpl_lanczos_pass_one_batch(tpl_op_t op, const double* B, int64_t b_len, size_t s,
+                                      size_t k, double* alphas, double* betas,
+                                      size_t* steps, double* b_norms, int mem);
+/* the decompositions as pass_one_batch wrote them (ld = the k they were made with);
+ * y: ld x s, column c holding steps[c] entries (already scaled by ||b_c||) */
+tpl_status tpl_lanczos_pass_two_batch(tpl_op_t op, const double* B, int64_t b_len, size_t s,
+                                      const double* alphas, const double* betas, size_t ld,
+                                      const size_t* steps, const double* b_norms,
+                                      const double* y, double* x_out, int mem);
 
 /* Where tpl_lanczos_two_pass evaluates the built-in f(T_k): mode 0 = host (two graphs
  * around the host call), 1 = device (the whole solve one graph), 2 = auto (default).

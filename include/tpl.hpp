@@ -486,6 +486,31 @@ inline Mat lanczos_multi(const HipCsrOp& op, const std::vector<double>& b, size_
                                return tpl_lanczos_multi(o, bp, n, kk, fn, u, m, x, TPL_MEM_HOST);
                              });
 }
+// One lock-step two-pass run for the s columns of B (n x s): pass one for all columns
+// together, f(T_k) e_1 per column on the host in column order, one pass two. Column c of the
+// n x s result is bitwise lanczos_two_pass's for B's column c with f evaluated on the host.
+inline Mat lanczos_two_pass_batch(const HipCsrOp& op, const Mat& B, size_t k,
+                                  const FtkSolver& f_tk_solver) {
+  if (B.rows != op.ncols()) throw LanczosError::dimension_mismatch(op.ncols(), B.rows);
+  Mat x(op.nrows(), B.cols);
+  tpl_ftk_fn fn = nullptr;
+  detail::FtkCall c{&f_tk_solver};
+  void* user = nullptr;
+  if (!detail::is_builtin(f_tk_solver, &fn)) {
+    fn = &detail::ftk_trampoline;
+    user = &c;
+  }
+  const tpl_status st = tpl_lanczos_two_pass_batch(op.handle(), B.data.data(), (int64_t)B.rows,
+                                                   B.cols, k, fn, user, x.data.data(),
+                                                   TPL_MEM_HOST);
+  if (st == TPL_ERR_PARAMETER_MISMATCH && c.cols_mismatch) {
+    tpl_error_detail d{};
+    tpl_last_error_detail(&d);
+    throw LanczosError::parameter_mismatch("y_k_prime", (size_t)d.expected, c.rows);
+  }
+  detail::check(st);
+  return x;
+}
 }  // namespace solvers
 
 // ---- low-level API: src/algorithms/ -----------------------------------------------------

@@ -132,6 +132,16 @@ extern "C" {
                                   alphas: *const f64, n_alphas: usize, betas: *const f64,
                                   n_betas: usize, steps: usize, b_norm: f64, y: *const f64,
                                   y_len: usize, m: usize, x_out: *mut f64, mem: c_int) -> c_int;
+    fn tpl_lanczos_two_pass_batch(op: *mut TplOp, B: *const f64, b_len: i64, s: usize, k: usize,
+                                  f: FtkFn, f_user: *mut c_void, x_out: *mut f64,
+                                  mem: c_int) -> c_int;
+    fn tpl_lanczos_pass_one_batch(op: *mut TplOp, B: *const f64, b_len: i64, s: usize, k: usize,
+                                  alphas: *mut f64, betas: *mut f64, steps: *mut usize,
+                                  b_norms: *mut f64, mem: c_int) -> c_int;
+    fn tpl_lanczos_pass_two_batch(op: *mut TplOp, B: *const f64, b_len: i64, s: usize,
+                                  alphas: *const f64, betas: *const f64, ld: usize,
+                                  steps: *const usize, b_norms: *const f64, y: *const f64,
+                                  x_out: *mut f64, mem: c_int) -> c_int;
     fn tpl_copy_to_host(dst: *mut c_void, src_device: *const c_void, bytes: usize) -> c_int;
     fn tpl_op_nrows(op: *mut TplOp) -> i64;
     fn tpl_op_local_rows(op: *mut TplOp, rows: *mut i64) -> c_int;
@@ -830,5 +840,36 @@ pub fn lanczos_pass_two_multi(
                                              TPL_MEM_HOST))?;
         }
         Ok(column_major(&x, op.n, m))
+    })?
+}
+
+/// f(A) b_1 ... f(A) b_s for the s columns of `b` (n x s) by ONE lock-step two-pass run (no
+/// reference counterpart: its solver takes one `b`): pass one for all columns together, the
+/// closure once per column in column order, one pass two. Column c is bitwise
+/// `lanczos_two_pass` of `b`'s column c with the closure evaluated on the host.
+pub fn lanczos_two_pass_batch<O, F>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    k: usize,
+    stack: &mut MemStack,
+    mut f_tk_solver: F,
+) -> Result<Mat<f64>, LanczosError>
+where
+    O: HipOperand,
+    F: FnMut(&[f64], &[f64]) -> Result<Mat<f64>, anyhow::Error>,
+{
+    let _ = stack;
+    let (n, s) = (b.nrows(), b.ncols());
+    let bv: Vec<f64> = (0..n * s).map(|t| b[(t % n, t / n)]).collect();
+    let user = &mut f_tk_solver as *mut F as *mut c_void;
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n * s];
+        let _g = op.lock.lock().unwrap();
+        unsafe {
+            check(tpl_lanczos_two_pass_batch(op.op, bv.as_ptr(), n as i64, s, k,
+                                             ftk_trampoline::<F> as FtkFn, user, x.as_mut_ptr(),
+                                             TPL_MEM_HOST))?;
+        }
+        Ok(column_major(&x, op.n, s))
     })?
 }

@@ -13,6 +13,9 @@
 //   tpl_k_ftk_exp.hip   k_ftk_exp
 //   tpl_k_multi.hip     k_p2_minit, k_p2_xacc (multi-function pass two: the x updates of
 //                       every column, with k_p2_spmv run at nflush = 0)
+//   tpl_k_batch_p1.hip  k_b_interleave / _deinterleave, k_bp1_init, k_bp1_spmv, k_bp1_axpy } the
+//   tpl_k_batch_p2.hip  k_bp2_init, k_bp2_coefs, k_bp2_spmv } lock-step batch solve: NB = 2 / 4
+//                       columns per launch (building blocks: tpl_kbatch.h, state: tpl_batch.h)
 //   tpl_k_dist_reorth.hip  k_long_epi_p1 / _y / _p2 (partitioned solve) and k_reorth_dot /
 //                       _reduce / _update / _decide: one unit, see its header
 //   tpl_kcommon.h       device building blocks: reductions, epilogues, the sliced-ELL chunk,

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "tpl_batch.h"
 #include "tpl_device.h"
 #include "tpl_internal.h"
 #include "tpl_launch.h"
@@ -77,6 +78,21 @@ struct SolverState {
   void* h_state = nullptr;  // pinned mirror of flags | norms | alphas | betas
   DevState S{};
   double* d_Pr = nullptr;   // reorthogonalisation partials (G * kcap)
+};
+
+// The buffers of a lock-step batch group (ensure_batch), for groups of nb columns and
+// kcap steps under the current layout; nb == 0: none. Interleaved work vectors (ld x nb
+// each): b, the ring R0..R2 (pass one's r, then pass two's v), W, x.
+struct BatchBufs {
+  int nb = 0;
+  size_t kcap = 0;
+  double* d_vecs = nullptr;
+  double *b = nullptr, *R[3] = {nullptr, nullptr, nullptr}, *W = nullptr, *x = nullptr;
+  void* d_state = nullptr;          // flags | norms | alphas | betas | y | p2c | Pa | Pb
+  double* d_P = nullptr;            // the long rows' hand-off slots, nb per slice
+  unsigned int* d_Pcnt = nullptr;   // and arrival counters of the batch's own
+  double* d_stage = nullptr;        // n x nb, column-major: host B in, host X out
+  BatchDev S{};
 };
 
 struct GraphExecDelete {
@@ -144,6 +160,7 @@ struct tpl_op_s {
   // apart) and the coefficient table Y (xcols columns, ycap apart); nullptr: xcols == 0
   double *d_X = nullptr, *d_Y = nullptr;
   size_t xcols = 0, ycap = 0;
+  tpl::BatchBufs bat;               // lock-step batch solves (ensure_batch)
   std::map<std::pair<int, size_t>, tpl::GraphExec> graphs;
   // device allocations of this operator (pointer -> bytes): tpl_op_device_bytes
   std::map<const void*, size_t> allocs;
@@ -206,6 +223,12 @@ void ensure_basis(tpl_op_s* op, size_t cols);
 // the state's current kcap (ensure_state first). They grow with m and kcap; growing drops
 // the cached graphs.
 void ensure_multi(tpl_op_s* op, size_t m);
+// The interleaved work vectors, per-column state and hand-off buffers of a batch group of
+// nb (2 or 4) columns and k steps, allocated on demand and counted in device_bytes. They
+// grow with nb and k; growing drops the cached graphs. A layout rebuild frees them
+// (free_batch): the next batch call allocates for the new layout.
+void ensure_batch(tpl_op_s* op, int nb, size_t k);
+void free_batch(tpl_op_s* op);
 double* ensure_view(tpl_op_s* op, size_t cols);
 // Per-step second-pass records of the selective re-orthogonalisation (slot j - 1: step j).
 int* reorth_records(const tpl_op_s* op);
@@ -266,6 +289,11 @@ void run_pass2(tpl_op_s* op, size_t steps);
 // Pass two for the m coefficient columns of op->d_Y into op->d_X (ensure_multi): one graph
 // per (steps, m).
 void run_pass2_multi(tpl_op_s* op, size_t steps, size_t m);
+// One group of a batch solve (ensure_batch first; the group's b interleaved in op->bat.b):
+// pass one for the nb columns in lock-step, one graph per (k, nb); pass
+// two up to the group's largest steps_taken, one graph per (kmax, nb).
+void run_pass1_batch(tpl_op_s* op, size_t k, int nb);
+void run_pass2_batch(tpl_op_s* op, size_t kmax, int nb);
 void run_two_pass_dev(tpl_op_s* op, size_t k, int f);
 HostDecomp fetch_decomp(tpl_op_s* op);
 

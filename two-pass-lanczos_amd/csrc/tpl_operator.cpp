@@ -247,6 +247,7 @@ void rebuild_schedule(tpl_op_s* op, const SchedParams& cand, int reorder) {
   drop_graphs(op);
   // partial buffers depend on the layout: force state reallocation
   op->st.kcap = 0;
+  free_batch(op);
 }
 
 // state layout: [flags: 8 int32 (kFlagBytes)] [norms kcap+1] [alphas kcap] [betas kcap] [y kcap]
@@ -336,6 +337,65 @@ void ensure_multi(tpl_op_s* op, size_t m) {
   dev_alloc(op, &op->d_Y, cols * cap * sizeof(double));
   op->xcols = cols;
   op->ycap = cap;
+}
+void free_batch(tpl_op_s* op) {
+  BatchBufs& b = op->bat;
+  dev_free(op, b.d_vecs), dev_free(op, b.d_state), dev_free(op, b.d_P), dev_free(op, b.d_Pcnt);
+  dev_free(op, b.d_stage);
+  b = BatchBufs{};
+}
+// Freed before they grow, as the basis is. State layout, per group: [flags: 8 int32 per
+// column] [norms nb (kc + 1)] [alphas nb kc] [betas nb kc] [y nb kc] | 64-B aligned:
+// [p2c 8 nb kc] [Pa nb NA] [Pb nb G2].
+void ensure_batch(tpl_op_s* op, int nb, size_t k) {
+  BatchBufs& b = op->bat;
+  if (nb <= b.nb && k <= b.kcap) return;
+  const int w = std::max(nb, b.nb);
+  const size_t kc = std::max<size_t>(std::max(k, b.kcap), 16);
+  drop_graphs(op);
+  free_batch(op);
+  const CsrDev A = csr_dev(op);
+  const size_t ld = (size_t)op->ld, na = (size_t)std::max(A.NA, 1), g2 = (size_t)std::max(A.G2, 1);
+  try {
+    dev_alloc(op, &b.d_vecs, 6 * ld * w * sizeof(double));
+    HIPCHK(hipMemset(b.d_vecs, 0, 6 * ld * w * sizeof(double)));
+    const size_t head = (size_t)w * (kFlagBytes / sizeof(double)) + (size_t)w * (4 * kc + 1);
+    const size_t p2c_off = (head + 7) / 8 * 8;
+    const size_t doubles = p2c_off + 8 * (size_t)w * kc + (size_t)w * (na + g2);
+    dev_alloc(op, &b.d_state, doubles * sizeof(double));
+    HIPCHK(hipMemset(b.d_state, 0, doubles * sizeof(double)));
+    const size_t nl = std::max<size_t>(op->lay.lrows.size(), 1);
+    dev_alloc(op, &b.d_P, nl * kSlotStride * kBatchNbMax * sizeof(double));
+    HIPCHK(hipMemset(b.d_P, 0, nl * kSlotStride * kBatchNbMax * sizeof(double)));
+    dev_alloc(op, &b.d_Pcnt, nl * kCntStride * sizeof(unsigned int));
+    HIPCHK(hipMemset(b.d_Pcnt, 0, nl * kCntStride * sizeof(unsigned int)));
+    dev_alloc(op, &b.d_stage, std::max<size_t>((size_t)op->part.n, 1) * w * sizeof(double));
+    double* p = b.d_vecs;
+    b.b = p, p += ld * w;
+    for (int i = 0; i < 3; ++i) b.R[i] = p, p += ld * w;
+    b.W = p, p += ld * w;
+    b.x = p;
+    double* base = (double*)b.d_state;
+    BatchDev& S = b.S;
+    S.flags = (int32_t*)base;
+    S.norms = base + (size_t)w * (kFlagBytes / sizeof(double));
+    S.alphas = S.norms + (size_t)w * (kc + 1);
+    S.betas = S.alphas + (size_t)w * kc;
+    S.y = S.betas + (size_t)w * kc;
+    S.p2c = base + p2c_off;
+    S.Pa = S.p2c + 8 * (size_t)w * kc;
+    S.Pb = S.Pa + (size_t)w * na;
+    S.P = b.d_P;
+    S.Pcnt = b.d_Pcnt;
+    S.kcap = (int32_t)kc;
+    S.na_ld = (int32_t)na;
+    S.g2_ld = (int32_t)g2;
+  } catch (...) {
+    free_batch(op);
+    throw;
+  }
+  b.nb = w;
+  b.kcap = kc;
 }
 // The step callback's view of V_k in the caller's row order: the basis itself, or (a
 // reordered operator) an n x cols buffer each batch's new columns are gathered into.

@@ -20,6 +20,8 @@ enum GraphKind {
   kGDevFtk,           // (timed variant) device f(T_k) + pass-two prologue
   kGPass2Dyn,         // (timed variant) the k - 1 step launches of a one-graph solve
   kGPass2Multi,       // pass two of a multi-function solve: one graph per (steps, m)
+  kGPass1Batch,       // pass one of a batch group: one graph per (k, NB)
+  kGPass2Batch,       // pass two of a batch group: one graph per (largest steps, NB)
 };
 // What tells one pass-one sequence (and its graph) from another, beside k: the basis is
 // stored (the standard pass), T_k's LU is eliminated as it goes (a device inv follows:
@@ -273,6 +275,45 @@ void run_pass2_multi(tpl_op_s* op, size_t steps, size_t m) {
     fail(TPL_ERR_INVALID_ARGUMENT, "run_pass2_multi: buffers smaller than the request");
   run_graph(op, kGPass2Multi, steps * (TPL_MULTI_MAX + 1) + m,
             [&] { enqueue_pass2_multi(op, steps, m); });
+}
+
+// ---- lock-step batch groups (tpl_lanczos_two_pass_batch): the single solve's launch
+// sequences with the batch kernels, over the group's interleaved vectors. r_1 = b, then
+// R[j % 3]; pass two reuses the ring for v (v_1 in R[1]).
+static void enqueue_pass1_batch(tpl_op_s* op, size_t k, int nb) {
+  const CsrDev A = csr_dev(op);
+  BatchBufs& bb = op->bat;
+  const BatchDev& S = bb.S;
+  HIPCHK(launch::bp1_init(nb, A, S, bb.b, op->stream));
+  auto r_of = [&](int j) { return j == 1 ? bb.b : bb.R[j % 3]; };
+  for (int j = 1; j <= (int)k; ++j) {
+    HIPCHK(launch::bp1_spmv(nb, A, S, r_of(j), j >= 2 ? r_of(j - 1) : nullptr, bb.W, j,
+                            op->stream));
+    HIPCHK(launch::bp1_axpy(nb, A, S, bb.W, r_of(j), bb.R[(j + 1) % 3], j, (int)k, op->stream));
+  }
+}
+static void enqueue_pass2_batch(tpl_op_s* op, size_t kmax, int nb) {
+  const CsrDev A = csr_dev(op);
+  BatchBufs& bb = op->bat;
+  const BatchDev& S = bb.S;
+  HIPCHK(launch::bp2_init(nb, A, S, bb.b, bb.R[1], bb.x, op->stream));
+  HIPCHK(launch::bp2_coefs(nb, S, (int)kmax, op->stream));
+  for (int j = 1; j < (int)kmax; ++j)
+    HIPCHK(launch::bp2_spmv(nb, A, S, bb.R[j % 3], j >= 2 ? bb.R[(j + 2) % 3] : nullptr,
+                            bb.R[(j + 1) % 3], bb.x, j, op->stream));
+}
+static void check_batch(const tpl_op_s* op, size_t k, int nb) {
+  if (op->dist) fail(TPL_ERR_UNSUPPORTED, "batch solve of a partitioned operator");
+  if ((nb != 2 && nb != 4) || nb > op->bat.nb || k > op->bat.kcap)
+    fail(TPL_ERR_INVALID_ARGUMENT, "batch group: buffers smaller than the request");
+}
+void run_pass1_batch(tpl_op_s* op, size_t k, int nb) {
+  check_batch(op, k, nb);
+  run_graph(op, kGPass1Batch, k * 8 + (size_t)nb, [&] { enqueue_pass1_batch(op, k, nb); });
+}
+void run_pass2_batch(tpl_op_s* op, size_t kmax, int nb) {
+  check_batch(op, kmax, nb);
+  run_graph(op, kGPass2Batch, kmax * 8 + (size_t)nb, [&] { enqueue_pass2_batch(op, kmax, nb); });
 }
 
 // Copy flags | norms[0] | alphas | betas back (one D2H), synchronise.

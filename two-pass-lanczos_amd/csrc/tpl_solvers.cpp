@@ -93,6 +93,58 @@ void write_decomp(const HostDecomp& d, double* alphas, double* betas, size_t* st
   *b_norm = d.b_norm;
 }
 
+// The two-pass solve with f(T_k) on the host (have_p1: pass one already ran).
+void two_pass_host_f(tpl_op_s* op, const double* b, size_t k, tpl_ftk_fn f, void* f_user,
+                     double* x_out, int mem, bool have_p1) {
+  // 1. pass one (src/solvers.rs:148)
+  op->last_one_graph = false;
+  if (!have_p1) run_pass_one(op, b, k, mem, false, false);
+  // 2. f(T_k) e_1 on the host (:155-165), 3. y = y' * ||b|| (:169)
+  const size_t steps = host_ftk(op, fetch_decomp(op), f, f_user, true, x_out, mem);
+  if (steps == 0) return;
+  // 4. pass two (:174)
+  run_pass2(op, steps);
+  download_vec(op, x_out, op->x, 1, mem);
+  sync_checked(op);
+}
+
+// Pass two for one decomposition (tpl_lanczos_pass_two after its argument checks).
+void pass_two_one(tpl_op_s* op, const double* b, const double* alphas, size_t n_alphas,
+                  const double* betas, size_t n_betas, size_t steps, double b_norm,
+                  const double* y, size_t y_len, double* x_out, double* v_out, int mem) {
+  // src/algorithms/lanczos_two_pass.rs:220-227
+  if (steps != y_len) fail_param_mismatch("y_k", steps, y_len);
+  // :229-235
+  if (b_norm <= kBreakdownTol)
+    fail_input("The initial vector `b` must not be a zero vector.");
+  if (steps == 0) { // :237-244
+    zero_out(op, x_out, mem);
+    return;
+  }
+  if (n_alphas < steps || n_betas + 1 < steps || !alphas || (steps > 1 && !betas) || !y)
+    fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
+  ensure_state(op, steps);
+  // decomposition -> device: norms[0], alphas, betas, y
+  const DevState& S = op->st.S;
+  HIPCHK(hipMemcpyAsync(S.norms, &b_norm, sizeof(double), hipMemcpyHostToDevice, op->stream));
+  HIPCHK(hipMemcpyAsync(S.alphas, alphas, steps * sizeof(double), hipMemcpyHostToDevice,
+                        op->stream));
+  if (steps > 1)
+    HIPCHK(hipMemcpyAsync(S.betas, betas, (steps - 1) * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+  HIPCHK(hipMemcpyAsync(S.y, y, steps * sizeof(double), hipMemcpyHostToDevice, op->stream));
+  upload_vec(op, op->b, b, mem);
+  if (v_out) {
+    ensure_basis(op, steps);
+    enqueue_pass2(op, steps, op->d_V);
+  } else {
+    run_pass2(op, steps);
+  }
+  download_vec(op, x_out, op->x, 1, mem);
+  if (v_out) download_vec(op, v_out, op->d_V, (int64_t)steps, mem);
+  sync_checked(op);
+}
+
 // Where a k-step solve evaluates f(T_k): on the device for the built-in inv / exp of an
 // operator that is not partitioned, up to the mode's k (tpl_op_set_device_ftk).
 DevF device_f(const tpl_op_s* op, tpl_ftk_fn f, size_t k) {
@@ -231,37 +283,8 @@ tpl_status tpl_lanczos_pass_two(tpl_op_t op, const double* b, int64_t b_len, con
     if (!op || !x_out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
     set_device(op);
     check_b(op, b, b_len);
-    // src/algorithms/lanczos_two_pass.rs:220-227
-    if (steps != y_len) fail_param_mismatch("y_k", steps, y_len);
-    // :229-235
-    if (b_norm <= kBreakdownTol)
-      fail_input("The initial vector `b` must not be a zero vector.");
-    if (steps == 0) { // :237-244
-      zero_out(op, x_out, mem);
-      return;
-    }
-    if (n_alphas < steps || n_betas + 1 < steps || !alphas || (steps > 1 && !betas) || !y)
-      fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
-    ensure_state(op, steps);
-    // decomposition -> device: norms[0], alphas, betas, y
-    const DevState& S = op->st.S;
-    HIPCHK(hipMemcpyAsync(S.norms, &b_norm, sizeof(double), hipMemcpyHostToDevice, op->stream));
-    HIPCHK(hipMemcpyAsync(S.alphas, alphas, steps * sizeof(double), hipMemcpyHostToDevice,
-                          op->stream));
-    if (steps > 1)
-      HIPCHK(hipMemcpyAsync(S.betas, betas, (steps - 1) * sizeof(double), hipMemcpyHostToDevice,
-                            op->stream));
-    HIPCHK(hipMemcpyAsync(S.y, y, steps * sizeof(double), hipMemcpyHostToDevice, op->stream));
-    upload_vec(op, op->b, b, mem);
-    if (v_out) {
-      ensure_basis(op, steps);
-      enqueue_pass2(op, steps, op->d_V);
-    } else {
-      run_pass2(op, steps);
-    }
-    download_vec(op, x_out, op->x, 1, mem);
-    if (v_out) download_vec(op, v_out, op->d_V, (int64_t)steps, mem);
-    sync_checked(op);
+    pass_two_one(op, b, alphas, n_alphas, betas, n_betas, steps, b_norm, y, y_len, x_out, v_out,
+                 mem);
   });
 }
 
@@ -296,16 +319,7 @@ tpl_status tpl_lanczos_two_pass(tpl_op_t op, const double* b, int64_t b_len, siz
       // expansion): the host solver on the same decomposition, then pass two again
       have_p1 = true;
     }
-    // 1. pass one (src/solvers.rs:148)
-    op->last_one_graph = false;
-    if (!have_p1) run_pass_one(op, b, k, mem, false, false);
-    // 2. f(T_k) e_1 on the host (:155-165), 3. y = y' * ||b|| (:169)
-    const size_t steps = host_ftk(op, fetch_decomp(op), f, f_user, true, x_out, mem);
-    if (steps == 0) return;
-    // 4. pass two (:174)
-    run_pass2(op, steps);
-    download_vec(op, x_out, op->x, 1, mem);
-    sync_checked(op);
+    two_pass_host_f(op, b, k, f, f_user, x_out, mem, have_p1);
   });
 }
 
@@ -523,6 +537,205 @@ tpl_status tpl_op_ftk_device(tpl_op_t op, int which, const double* alphas, size_
     HIPCHK(hipMemcpyAsync(flags, S.flags, kFlagBytes, hipMemcpyDeviceToHost, op->stream));
     sync_checked(op);
     *on_device = flags[4] ? 0 : 1;
+  });
+}
+
+} // extern "C"
+
+// ---- f(A) b_1 ... f(A) b_s in one lock-step run ---------------------------------------
+namespace {
+// The grouping rule (DESIGN.md §2 "Several right-hand sides in lock-step", include/tpl.h):
+// the columns are taken in order, four at a time while four remain, then two at a time;
+// a last single column runs the single host-f solve. No group is padded: a remainder of
+// three is a group of two and a single solve (a padded group of four measured slower than
+// three single solves).
+int group_width(size_t rem) { return rem >= 4 ? 4 : (rem >= 2 ? 2 : 1); }
+
+void check_batch_args(tpl_op_s* op, bool have_args, size_t s) {
+  if (!op || !have_args) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (s == 0 || s > (size_t)TPL_BATCH_MAX)
+    fail(TPL_ERR_INVALID_ARGUMENT, "s must be between 1 and TPL_BATCH_MAX");
+  set_device(op);
+  if (op->dist) fail(TPL_ERR_UNSUPPORTED, "batch solve of a partitioned operator");
+}
+
+// Host mirror of a group's state head: flags | norms | alphas | betas (| y), laid out as
+// ensure_batch laid out the device block.
+struct GroupHead {
+  std::vector<double> h;
+  size_t w, kc;
+  explicit GroupHead(const tpl_op_s* op)
+      : w((size_t)op->bat.nb), kc(op->bat.kcap) {
+    h.assign(w * (kFlagBytes / sizeof(double)) + w * (4 * kc + 1), 0.0);
+  }
+  int32_t* flags(size_t c) { return reinterpret_cast<int32_t*>(h.data()) + 8 * c; }
+  double* norms(size_t c) { return h.data() + w * (kFlagBytes / sizeof(double)) + c * (kc + 1); }
+  double* alphas(size_t c) { return norms(0) + w * (kc + 1) + c * kc; }
+  double* betas(size_t c) { return alphas(0) + w * kc + c * kc; }
+  double* y(size_t c) { return betas(0) + w * kc + c * kc; }
+  size_t decomp_bytes() const { return (h.size() - w * kc) * sizeof(double); }
+  HostDecomp decomp(size_t c) {
+    HostDecomp d;
+    std::memcpy(d.flags, flags(c), kFlagBytes);
+    d.b_norm = norms(c)[0];
+    d.alphas = alphas(c);
+    d.betas = betas(c);
+    d.steps = (size_t)d.flags[2];
+    return d;
+  }
+};
+
+// The nb columns of the caller's B (column-major, ld = n) into the group's
+// interleaved b, in the operator's order.
+void upload_group(tpl_op_s* op, const double* B, int nb, int mem) {
+  const int64_t n = op->part.n;
+  const double* src = B;
+  if (mem != TPL_MEM_DEVICE) {
+    HIPCHK(hipMemcpyAsync(op->bat.d_stage, B, (size_t)n * nb * sizeof(double),
+                          hipMemcpyHostToDevice, op->stream));
+    src = op->bat.d_stage;
+  }
+  HIPCHK(launch::b_interleave(nb, n, op->bat.b, src, op->bufs.d_perm, op->stream));
+}
+// The group's interleaved x out to the nb columns of the caller's X.
+void download_group(tpl_op_s* op, double* X, int nb, int mem) {
+  const int64_t n = op->part.n;
+  double* dst = mem == TPL_MEM_DEVICE ? X : op->bat.d_stage;
+  HIPCHK(launch::b_deinterleave(nb, n, dst, op->bat.x, op->bufs.d_iperm, op->stream));
+  if (mem != TPL_MEM_DEVICE)
+    HIPCHK(hipMemcpyAsync(X, op->bat.d_stage, (size_t)n * nb * sizeof(double),
+                          hipMemcpyDeviceToHost, op->stream));
+}
+// Pass one of a group; returns the decompositions' host mirror (synchronised).
+GroupHead pass_one_group(tpl_op_s* op, const double* B, size_t k, int nb, int mem) {
+  ensure_batch(op, nb, k);
+  upload_group(op, B, nb, mem);
+  run_pass1_batch(op, k, nb);
+  GroupHead g(op);
+  HIPCHK(hipMemcpyAsync(g.h.data(), op->bat.d_state, g.decomp_bytes(), hipMemcpyDeviceToHost,
+                        op->stream));
+  sync_checked(op);
+  return g;
+}
+} // namespace
+
+extern "C" {
+
+tpl_status tpl_lanczos_two_pass_batch(tpl_op_t op, const double* B, int64_t b_len, size_t s,
+                                      size_t k, tpl_ftk_fn f, void* f_user, double* x_out,
+                                      int mem) {
+  return guarded([&] {
+    check_batch_args(op, B && x_out && f, s);
+    check_b(op, B, b_len);
+    check_k(k);
+    const TimingOff untimed(op);
+    op->last_one_graph = false;
+    const size_t n = (size_t)op->part.n;
+    for (size_t c0 = 0; c0 < s;) {
+      const int nb = n == 0 ? 1 : group_width(s - c0);
+      if (nb == 1) {  // the single solve's host-f path
+        two_pass_host_f(op, B + c0 * n, k, f, f_user, x_out + c0 * n, mem, false);
+        ++c0;
+        continue;
+      }
+      // 1. pass one for the group's columns in lock-step
+      GroupHead g = pass_one_group(op, B + c0 * n, k, nb, mem);
+      // 2. f(T_k) e_1 per column on the host, in column order, 3. y_c = y'_c * ||b_c||
+      size_t kmax = 0;
+      std::vector<double> y;
+      for (int c = 0; c < nb; ++c) {
+        const HostDecomp d = g.decomp((size_t)c);
+        if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+        call_ftk(f, f_user, d, y);
+        for (size_t j = 0; j < d.steps; ++j) g.y((size_t)c)[j] = y[j] * d.b_norm;
+        kmax = std::max(kmax, d.steps);
+      }
+      HIPCHK(hipMemcpyAsync(op->bat.S.y, g.y(0), g.w * g.kc * sizeof(double),
+                            hipMemcpyHostToDevice, op->stream));
+      // 4. one pass two for all of them
+      run_pass2_batch(op, kmax, nb);
+      download_group(op, x_out + c0 * n, nb, mem);
+      sync_checked(op);
+      c0 += (size_t)nb;
+    }
+  });
+}
+
+tpl_status tpl_lanczos_pass_one_batch(tpl_op_t op, const double* B, int64_t b_len, size_t s,
+                                      size_t k, double* alphas, double* betas, size_t* steps,
+                                      double* b_norms, int mem) {
+  return guarded([&] {
+    check_batch_args(op, B && alphas && betas && steps && b_norms, s);
+    check_b(op, B, b_len);
+    check_k(k);
+    const TimingOff untimed(op);
+    const size_t n = (size_t)op->part.n;
+    for (size_t c0 = 0; c0 < s;) {
+      const int nb = n == 0 ? 1 : group_width(s - c0);
+      if (nb == 1) {
+        run_pass_one(op, B + c0 * n, k, mem, false, false);
+        write_decomp(fetch_decomp(op), alphas + c0 * k, betas + c0 * k, steps + c0, b_norms + c0);
+        ++c0;
+        continue;
+      }
+      GroupHead g = pass_one_group(op, B + c0 * n, k, nb, mem);
+      for (int c = 0; c < nb; ++c)
+        write_decomp(g.decomp((size_t)c), alphas + (c0 + c) * k, betas + (c0 + c) * k,
+                     steps + c0 + c, b_norms + c0 + c);
+      c0 += (size_t)nb;
+    }
+  });
+}
+
+tpl_status tpl_lanczos_pass_two_batch(tpl_op_t op, const double* B, int64_t b_len, size_t s,
+                                      const double* alphas, const double* betas, size_t ld,
+                                      const size_t* steps, const double* b_norms,
+                                      const double* y, double* x_out, int mem) {
+  return guarded([&] {
+    check_batch_args(op, B && x_out && steps && b_norms, s);
+    check_b(op, B, b_len);
+    const TimingOff untimed(op);
+    // the single call's checks, per column in ascending order
+    for (size_t c = 0; c < s; ++c) {
+      if (b_norms[c] <= kBreakdownTol)
+        fail_input("The initial vector `b` must not be a zero vector.");
+      if (steps[c] > ld || (steps[c] > 0 && (!alphas || !y)) || (steps[c] > 1 && !betas))
+        fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
+      if (steps[c] > (size_t)INT32_MAX / 2) fail(TPL_ERR_INVALID_ARGUMENT, "steps too large");
+    }
+    const size_t n = (size_t)op->part.n;
+    for (size_t c0 = 0; c0 < s;) {
+      const int nb = n == 0 ? 1 : group_width(s - c0);
+      if (nb == 1) {
+        const size_t st = steps[c0];
+        // (NULL arrays are accepted when no column takes a step: no arithmetic on them)
+        auto col = [&](const double* p) { return p ? p + c0 * ld : nullptr; };
+        pass_two_one(op, B + c0 * n, col(alphas), st, col(betas), st > 0 ? st - 1 : 0, st,
+                     b_norms[c0], col(y), st, x_out + c0 * n, nullptr, mem);
+        ++c0;
+        continue;
+      }
+      size_t kmax = 1;
+      for (int c = 0; c < nb; ++c) kmax = std::max(kmax, steps[c0 + c]);
+      ensure_batch(op, nb, kmax);
+      // decompositions -> the group's state: steps_c, ||b_c||, alphas, betas, y
+      GroupHead g(op);
+      for (int c = 0; c < nb; ++c) {
+        const size_t cc = c0 + (size_t)c, st = steps[cc];
+        g.flags((size_t)c)[2] = (int32_t)st;
+        g.norms((size_t)c)[0] = b_norms[cc];
+        if (st > 0) std::memcpy(g.alphas((size_t)c), alphas + cc * ld, st * sizeof(double));
+        if (st > 1) std::memcpy(g.betas((size_t)c), betas + cc * ld, (st - 1) * sizeof(double));
+        if (st > 0) std::memcpy(g.y((size_t)c), y + cc * ld, st * sizeof(double));
+      }
+      HIPCHK(hipMemcpyAsync(op->bat.d_state, g.h.data(), g.h.size() * sizeof(double),
+                            hipMemcpyHostToDevice, op->stream));
+      upload_group(op, B + c0 * n, nb, mem);
+      run_pass2_batch(op, kmax, nb);
+      download_group(op, x_out + c0 * n, nb, mem);
+      sync_checked(op);
+      c0 += (size_t)nb;
+    }
   });
 }
 

@@ -112,6 +112,14 @@ tpl_lanczos_multi = _sig("tpl_lanczos_multi", c_int, c_void_p, c_void_p, c_int64
 tpl_lanczos_pass_two_multi = _sig("tpl_lanczos_pass_two_multi", c_int, c_void_p, c_void_p, c_int64,
                                   PD, c_size_t, PD, c_size_t, c_size_t, c_double, PD, c_size_t,
                                   c_size_t, c_void_p, c_int)
+TPL_BATCH_MAX = 64
+tpl_lanczos_two_pass_batch = _sig("tpl_lanczos_two_pass_batch", c_int, c_void_p, c_void_p, c_int64,
+                                  c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_int)
+tpl_lanczos_pass_one_batch = _sig("tpl_lanczos_pass_one_batch", c_int, c_void_p, c_void_p, c_int64,
+                                  c_size_t, c_size_t, PD, PD, POINTER(c_size_t), PD, c_int)
+tpl_lanczos_pass_two_batch = _sig("tpl_lanczos_pass_two_batch", c_int, c_void_p, c_void_p, c_int64,
+                                  c_size_t, PD, PD, c_size_t, POINTER(c_size_t), PD, PD, c_void_p,
+                                  c_int)
 tpl_load_kkt_system = _sig("tpl_load_kkt_system", c_int, c_char_p, c_char_p, POINTER(CsrHost))
 tpl_csr_host_free = _sig("tpl_csr_host_free", None, POINTER(CsrHost))
 tpl_generate_kkt = _sig("tpl_generate_kkt", c_int, c_int64, c_int64, ctypes.c_uint64,
@@ -229,6 +237,8 @@ tpl_plan_create = _sig("tpl_plan_create", c_int, c_int64, POINTER(c_int64), POIN
                        c_int, c_int, c_int, c_int32, POINTER(c_void_p))
 EXPORTED += ["tpl_plan_create"]
 EXPORTED += ["tpl_lanczos_two_pass_multi", "tpl_lanczos_multi", "tpl_lanczos_pass_two_multi"]
+EXPORTED += ["tpl_lanczos_two_pass_batch", "tpl_lanczos_pass_one_batch",
+             "tpl_lanczos_pass_two_batch"]
 EXPORTED += ["tpl_dist_op_create_replicated", "tpl_op_local_rows", "tpl_dist_partition", "tpl_dist_unique_id", "tpl_dist_create",
              "tpl_dist_create_host", "tpl_dist_destroy", "tpl_dist_op_create_csr",
              "tpl_dist_op_create_halo", "tpl_dist_choose_partition", "tpl_dist_op_create_auto",

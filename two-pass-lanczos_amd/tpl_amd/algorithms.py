@@ -12,6 +12,8 @@ this module                            reference
 ``lanczos_pass_two``                   src/algorithms/lanczos_two_pass.rs:128-140
 ``lanczos_pass_two_with_basis``        src/algorithms/lanczos_two_pass.rs:149-166
 ``lanczos_pass_two_multi``             (none: pass two for m coefficient vectors at once)
+``lanczos_pass_one_batch``             (none: pass one for s vectors b in lock-step)
+``lanczos_pass_two_batch``             (none: pass two for s vectors b in lock-step)
 =====================================  ================================================
 
 Every call runs the recurrence on the GPU through libtpl_amd.so (C ABI,
@@ -28,8 +30,8 @@ from typing import Callable, Optional
 import numpy as np
 
 from . import _lib
-from ._vec import Vec
-from .error import check
+from ._vec import Cols, Vec
+from .error import LanczosError, check
 from .operator import HipCsrOp, as_operator
 
 BREAKDOWN_TOLERANCE = 1000.0 * np.finfo(np.float64).eps  # src/algorithms/mod.rs:140-143
@@ -203,5 +205,69 @@ def lanczos_pass_two_multi(operator, b, decomposition: LanczosDecomposition, Y):
         op.handle, bv.ptr, bv.n, a.ctypes.data_as(POINTER(c_double)), a.shape[0],
         bb.ctypes.data_as(POINTER(c_double)), bb.shape[0], int(decomposition.steps_taken),
         float(decomposition.b_norm), yt.ctypes.data_as(POINTER(c_double)), y_len, m,
+        Vec.ptr_of(x), bv.mem))
+    return x.T
+
+
+def lanczos_pass_one_batch(operator, B, k: int) -> list:
+    """First pass for every column of ``B`` (n x s) in lock-step: a list of s
+    ``LanczosDecomposition``; entry c is bitwise ``lanczos_pass_one`` of ``B[:, c]``."""
+    bv = Cols(B)
+    bv.check_rows(operator)
+    op = _op(operator)
+    kk = max(k, 1)
+    alphas = np.zeros((bv.s, kk))  # C-order (s, k) == column-major (k, s)
+    betas = np.zeros((bv.s, kk))
+    steps = (c_size_t * bv.s)()
+    bnorms = np.zeros(bv.s)
+    check(_lib.tpl_lanczos_pass_one_batch(
+        op.handle, bv.ptr, bv.n, bv.s, k, alphas.ctypes.data_as(POINTER(c_double)),
+        betas.ctypes.data_as(POINTER(c_double)), steps, bnorms.ctypes.data_as(POINTER(c_double)),
+        bv.mem))
+    out = []
+    for c in range(bv.s):
+        st = int(steps[c])
+        out.append(LanczosDecomposition(alphas[c, :st].copy(), betas[c, :max(st - 1, 0)].copy(),
+                                        st, float(bnorms[c])))
+    return out
+
+
+def lanczos_pass_two_batch(operator, B, decompositions, ys):
+    """Second pass for every column of ``B`` in lock-step: ``decompositions[c]`` and
+    ``ys[c]`` (= f(T_k) e_1 * ||b_c||, ``steps_taken`` entries) belong to ``B[:, c]``.
+    Returns shape (n, s) with strides (1, n); column c is bitwise ``lanczos_pass_two``."""
+    bv = Cols(B)
+    bv.check_rows(operator)
+    decs, ys = list(decompositions), list(ys)
+    if len(decs) != bv.s or len(ys) != bv.s:
+        raise ValueError("one decomposition and one y per column of B")
+    op = _op(operator)
+    yl = [y.detach().double().cpu().numpy().reshape(-1) if hasattr(y, "is_cuda")
+          else np.asarray(y, dtype=np.float64).reshape(-1) for y in ys]
+    for d, y in zip(decs, yl):  # the single call's check, per column in ascending order
+        if int(d.steps_taken) != y.shape[0]:
+            raise LanczosError.parameter_mismatch("y_k", int(d.steps_taken), y.shape[0])
+    ld = max([int(d.steps_taken) for d in decs] + [1])
+    alphas = np.zeros((bv.s, ld))
+    betas = np.zeros((bv.s, ld))
+    yy = np.zeros((bv.s, ld))
+    steps = (c_size_t * bv.s)()
+    bnorms = np.zeros(bv.s)
+    for c, (d, y) in enumerate(zip(decs, yl)):
+        st = int(d.steps_taken)
+        a = np.asarray(d.alphas, dtype=np.float64).reshape(-1)
+        b = np.asarray(d.betas, dtype=np.float64).reshape(-1)
+        if a.shape[0] < st or b.shape[0] + 1 < st:
+            raise ValueError("decomposition arrays shorter than steps_taken")
+        alphas[c, :st] = a[:st]
+        betas[c, :max(st - 1, 0)] = b[:max(st - 1, 0)]
+        yy[c, :st] = y
+        steps[c] = st
+        bnorms[c] = float(d.b_norm)
+    x = bv.empty(bv.s, bv.n)
+    check(_lib.tpl_lanczos_pass_two_batch(
+        op.handle, bv.ptr, bv.n, bv.s, alphas.ctypes.data_as(POINTER(c_double)),
+        betas.ctypes.data_as(POINTER(c_double)), ld, steps,
+        bnorms.ctypes.data_as(POINTER(c_double)), yy.ctypes.data_as(POINTER(c_double)),
         Vec.ptr_of(x), bv.mem))
     return x.T

@@ -15,13 +15,18 @@ shape of ``b`` flattened to (n,) — numpy for host ``b``, torch CUDA for device
 counterpart) solve f_1(A) b ... f_m(A) b over one Krylov space: one pass one, every f_i on
 the host, one pass two. They return shape (n, m) with strides (1, n) — column i is bitwise
 the single solve with ``f_tk_solvers[i]`` evaluated on the host.
+
+``lanczos_two_pass_batch(operator, B, k, f_tk_solver)`` (no reference counterpart) solves
+f(A) b_1 ... f(A) b_s for the columns of ``B`` in one lock-step two-pass run. It returns shape
+(n, s) with strides (1, n) — column c is bitwise the single solve of ``B[:, c]`` with
+``f_tk_solver`` evaluated on the host.
 """
 from __future__ import annotations
 
 import ctypes
 
 from . import _lib, ftk
-from ._vec import Vec
+from ._vec import Cols, Vec
 from .error import LanczosError, check
 from .operator import as_operator
 
@@ -79,3 +84,20 @@ def lanczos_two_pass_multi(operator, b, k: int, f_tk_solvers):
     """f_i(A) b, i = 0 .. m-1, by ONE two-pass run: pass one once, every f_i(T_k) on the
     host, one pass two that regenerates the basis once for all m results."""
     return _run_multi(_lib.tpl_lanczos_two_pass_multi, operator, b, k, f_tk_solvers)
+
+
+def lanczos_two_pass_batch(operator, B, k: int, f_tk_solver):
+    """f(A) b_c for every column of ``B`` (n x s; a 1-D ``B`` is one column) by ONE lock-step
+    two-pass run: pass one for all columns together, f(T_k) per column on the host in column
+    order, one pass two. Each column keeps its own steps_taken."""
+    bv = Cols(B)
+    bv.check_rows(operator)
+    operator = as_operator(operator)
+    x = bv.empty(bv.s, bv.n)  # C-order (s, n) == column-major (n, s)
+    fptr, keep = ftk.resolve(f_tk_solver)
+    try:
+        check(_lib.tpl_lanczos_two_pass_batch(operator.handle, bv.ptr, bv.n, bv.s, k, fptr, None,
+                                              Vec.ptr_of(x), bv.mem))
+    except LanczosError as e:
+        raise ftk.remap_error(e, keep) from None
+    return x.T
