@@ -271,6 +271,43 @@ tpl_status tpl_lanczos_pass_two_batch(tpl_op_t op, const double* B, int64_t b_le
                                       const double* alphas, const double* betas, size_t ld,
                                       const size_t* steps, const double* b_norms,
                                       const double* y, double* x_out, int mem);
+/* ---- f_i(A) b_c: m functions of s right-hand sides in one run (both axes at once) ------
+ * X(c, i) = f_i(A) b_c, e.g. (A + sigma_i I)^-1 B for the poles of a rational approximation,
+ * or exp(t_i A) b_c for several states and times. Per group of columns, pass one runs in
+ * lock-step (as the batch solve's), every f_i runs on the host on every column's T_k, and
+ * ONE pass two regenerates the group's bases once and accumulates all results of the group.
+ * x_out is column-major n x (s m) with leading dimension n, the m results of b_c adjacent:
+ * column (c m + i).
+ * Parity: column (c, i) is bitwise tpl_lanczos_two_pass(op, b_c, k, fs[i]) with f(T_k) on
+ * the host (tpl_op_set_device_ftk(op, 0)); hence also column i of tpl_lanczos_two_pass_multi
+ * on b_c and column c of tpl_lanczos_two_pass_batch under fs[i]. It does not depend on s, on
+ * m, on its position, or on what the other columns hold, non-finite values included. A
+ * column that breaks down at step j_c keeps steps_c = j_c for all its m results; the others
+ * run on to their own end.
+ * Grouping: the batch solve's rule, unchanged: four columns per group while four remain,
+ * then two, no group padded; a last single column runs the multi-function solve of that
+ * b. m == 1 is the batch solve, s == 1 the multi-function solve.
+ * Call order of f: per group, pass one first; then for each column c ascending the batch
+ * solve's zero-vector check of that column, then fs[0..m) in index order on that column's
+ * T_k, each exactly once, with f_users[i] (f_users may be NULL). The first failure ends the
+ * call with the single solve's error text and detail. On an error x_out is unspecified.
+ * f is always evaluated on the host (tpl_op_flags bit 5 reads 0 afterwards); live timing is
+ * untouched (tpl_op_pass_timing keeps the last single solve's values).
+ * s == 0, s > TPL_BATCH_MAX, m == 0, m > TPL_MULTI_MAX, NULL B / fs / x_out (pass_two: NULL
+ * B / x_out / steps / b_norms, or arrays shorter than a column's steps):
+ * TPL_ERR_INVALID_ARGUMENT; a partitioned operator: TPL_ERR_UNSUPPORTED; a host-only plan is
+ * refused as by every solver. Not supported: v_out, re-orthogonalisation, device f(T_k). */
+tpl_status tpl_lanczos_two_pass_batch_multi(tpl_op_t op, const double* B, int64_t b_len,
+                                            size_t s, size_t k, const tpl_ftk_fn* fs,
+                                            void** f_users, size_t m, double* x_out, int mem);
+/* the decompositions as tpl_lanczos_pass_one_batch wrote them; y: column (c m + i) at
+ * y + (c m + i) ld, holding steps[c] entries already scaled by ||b_c||. Result (c, i) is
+ * bitwise tpl_lanczos_pass_two's for b_c and that y column. Every group of four or two
+ * columns runs the fused pass two, whatever m. */
+tpl_status tpl_lanczos_pass_two_batch_multi(tpl_op_t op, const double* B, int64_t b_len,
+                                            size_t s, const double* alphas, const double* betas,
+                                            size_t ld, const size_t* steps, const double* b_norms,
+                                            const double* y, size_t m, double* x_out, int mem);
 
 /* Where tpl_lanczos_two_pass evaluates the built-in f(T_k): mode 0 = host (two graphs
  * around the host call), 1 = device (the whole solve one graph), 2 = auto (default).

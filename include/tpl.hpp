@@ -511,6 +511,41 @@ inline Mat lanczos_two_pass_batch(const HipCsrOp& op, const Mat& B, size_t k,
   detail::check(st);
   return x;
 }
+// Both axes in one run: f_i(A) b_c for the m solvers and the s columns of B (n x s). Per group
+// of columns pass one runs in lock-step, every f_i(T_k) e_1 on the host (column by column,
+// the solvers in index order), and one pass two regenerates the group's bases once. Column
+// (c m + i) of the n x (s m) result is bitwise lanczos_two_pass's for B's column c with
+// f_tk_solvers[i] evaluated on the host.
+inline Mat lanczos_two_pass_batch_multi(const HipCsrOp& op, const Mat& B, size_t k,
+                                        const std::vector<FtkSolver>& f_tk_solvers) {
+  if (B.rows != op.ncols()) throw LanczosError::dimension_mismatch(op.ncols(), B.rows);
+  const size_t m = f_tk_solvers.size();
+  Mat x(op.nrows(), B.cols * m);
+  std::vector<detail::FtkCall> calls(m);
+  std::vector<tpl_ftk_fn> fns(m);
+  std::vector<void*> users(m);
+  for (size_t i = 0; i < m; ++i) {
+    calls[i].f = &f_tk_solvers[i];
+    if (detail::is_builtin(f_tk_solvers[i], &fns[i])) {
+      users[i] = nullptr;
+    } else {
+      fns[i] = &detail::ftk_trampoline;
+      users[i] = &calls[i];
+    }
+  }
+  const tpl_status st =
+      tpl_lanczos_two_pass_batch_multi(op.handle(), B.data.data(), (int64_t)B.rows, B.cols, k,
+                                       fns.data(), users.data(), m, x.data.data(), TPL_MEM_HOST);
+  if (st == TPL_ERR_PARAMETER_MISMATCH)
+    for (const detail::FtkCall& c : calls)  // the first failure ends the call: at most one is marked
+      if (c.cols_mismatch) {
+        tpl_error_detail d{};
+        tpl_last_error_detail(&d);
+        throw LanczosError::parameter_mismatch("y_k_prime", (size_t)d.expected, c.rows);
+      }
+  detail::check(st);
+  return x;
+}
 }  // namespace solvers
 
 // ---- low-level API: src/algorithms/ -----------------------------------------------------

@@ -142,6 +142,13 @@ extern "C" {
                                   alphas: *const f64, betas: *const f64, ld: usize,
                                   steps: *const usize, b_norms: *const f64, y: *const f64,
                                   x_out: *mut f64, mem: c_int) -> c_int;
+    fn tpl_lanczos_two_pass_batch_multi(op: *mut TplOp, B: *const f64, b_len: i64, s: usize,
+                                        k: usize, fs: *const FtkFn, f_users: *mut *mut c_void,
+                                        m: usize, x_out: *mut f64, mem: c_int) -> c_int;
+    fn tpl_lanczos_pass_two_batch_multi(op: *mut TplOp, B: *const f64, b_len: i64, s: usize,
+                                        alphas: *const f64, betas: *const f64, ld: usize,
+                                        steps: *const usize, b_norms: *const f64, y: *const f64,
+                                        m: usize, x_out: *mut f64, mem: c_int) -> c_int;
     fn tpl_copy_to_host(dst: *mut c_void, src_device: *const c_void, bytes: usize) -> c_int;
     fn tpl_op_nrows(op: *mut TplOp) -> i64;
     fn tpl_op_local_rows(op: *mut TplOp, rows: *mut i64) -> c_int;
@@ -871,5 +878,39 @@ where
                                              TPL_MEM_HOST))?;
         }
         Ok(column_major(&x, op.n, s))
+    })?
+}
+
+/// f_i(A) b_c for the m closures and the s columns of `b` (n x s) by ONE run (no reference
+/// counterpart): per group of columns pass one in lock-step, every closure once per column
+/// (column by column, the closures in index order), one pass two. Column (c m + i) of the
+/// n x (s m) result is bitwise `lanczos_two_pass` of `b`'s column c with `f_tk_solvers[i]`.
+pub fn lanczos_two_pass_batch_multi<O, F>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    k: usize,
+    stack: &mut MemStack,
+    f_tk_solvers: &mut [F],
+) -> Result<Mat<f64>, LanczosError>
+where
+    O: HipOperand,
+    F: FnMut(&[f64], &[f64]) -> Result<Mat<f64>, anyhow::Error>,
+{
+    let _ = stack;
+    let (n, s) = (b.nrows(), b.ncols());
+    let bv: Vec<f64> = (0..n * s).map(|t| b[(t % n, t / n)]).collect();
+    let m = f_tk_solvers.len();
+    let fns: Vec<FtkFn> = vec![ftk_trampoline::<F> as FtkFn; m];
+    let mut users: Vec<*mut c_void> =
+        f_tk_solvers.iter_mut().map(|f| f as *mut F as *mut c_void).collect();
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n * s * m];
+        let _g = op.lock.lock().unwrap();
+        unsafe {
+            check(tpl_lanczos_two_pass_batch_multi(op.op, bv.as_ptr(), n as i64, s, k,
+                                                   fns.as_ptr(), users.as_mut_ptr(), m,
+                                                   x.as_mut_ptr(), TPL_MEM_HOST))?;
+        }
+        Ok(column_major(&x, op.n, s * m))
     })?
 }

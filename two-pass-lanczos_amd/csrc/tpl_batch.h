@@ -14,6 +14,10 @@
 namespace tpl {
 
 constexpr int kBatchNbMax = 4;  // the widest group (instances: NB = 2 and NB = 4)
+// Functions per k_bp2_xacc launch (tpl_k_batch_multi.hip; instances M = 1 .. 4 per NB): at
+// NB = 4 the three ring vectors and M result vectors are 8 (3 + M) VGPRs of loads in flight
+// per element, 56 at M = 4; more functions run as further launches.
+constexpr int kBatchMultiFuncs = 4;
 
 // Per-column solver state of a group (the batch sibling of DevState; kcap, na_ld and g2_ld
 // are the column strides). Column c of the group reads and writes only its own part.
@@ -55,5 +59,20 @@ hipError_t bp2_init(int nb, const CsrDev& A, const BatchDev& B, const double* b,
 hipError_t bp2_coefs(int nb, const BatchDev& B, int kmax, hipStream_t s);
 hipError_t bp2_spmv(int nb, const CsrDev& A, const BatchDev& B, const double* v_cur,
                     const double* v_prev, double* v_next, double* x, int j, hipStream_t s);
+// ---- m functions of every column of a group (tpl_k_batch_multi.hip). Function f's result
+// is the interleaved group vector X + f xstride; its coefficients for column c are
+// Y[(f nb + c) B.kcap + j].
+hipError_t bp2_minit(int nb, const CsrDev& A, const BatchDev& B, const double* Y, int m,
+                     const double* b, double* v1, double* X, int64_t xstride, hipStream_t s);
+// bp2_coefs with every column's nflush 0: bp2_spmv then leaves x alone
+hipError_t bp2_coefs0(int nb, const BatchDev& B, int kmax, hipStream_t s);
+// the grouped flush after step j for m (1 .. kBatchMultiFuncs) functions, each column by
+// its own device-held steps_c; vp / vc / vn: v_{j-1}, v_j, v_{j+1}
+hipError_t bp2_xacc(int nb, const CsrDev& A, const BatchDev& B, const double* Y, int j,
+                    const double* vp, const double* vc, const double* vn, double* X,
+                    int64_t xstride, int m, hipStream_t s);
+// X[(c m + f) n + i] = in[f xstride + idx[i] nb + c] (idx == nullptr: identity)
+hipError_t bm_deinterleave(int nb, int64_t n, double* X, const double* in, int64_t xstride,
+                           int m, const int32_t* idx, hipStream_t s);
 } // namespace launch
 } // namespace tpl

@@ -16,6 +16,8 @@
 //   tpl_k_batch_p1.hip  k_b_interleave / _deinterleave, k_bp1_init, k_bp1_spmv, k_bp1_axpy } the
 //   tpl_k_batch_p2.hip  k_bp2_init, k_bp2_coefs, k_bp2_spmv } lock-step batch solve: NB = 2 / 4
 //                       columns per launch (building blocks: tpl_kbatch.h, state: tpl_batch.h)
+//   tpl_k_batch_multi.hip  k_bp2_minit, k_bp2_coefs0, k_bp2_xacc, k_bm_deinterleave (m functions
+//                       of every column of a group: the x updates, with k_bp2_spmv run at nflush = 0)
 //   tpl_k_dist_reorth.hip  k_long_epi_p1 / _y / _p2 (partitioned solve) and k_reorth_dot /
 //                       _reduce / _update / _decide: one unit, see its header
 //   tpl_kcommon.h       device building blocks: reductions, epilogues, the sliced-ELL chunk,

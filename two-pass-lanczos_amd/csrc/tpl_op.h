@@ -92,6 +92,13 @@ struct BatchBufs {
   double* d_P = nullptr;            // the long rows' hand-off slots, nb per slice
   unsigned int* d_Pcnt = nullptr;   // and arrival counters of the batch's own
   double* d_stage = nullptr;        // n x nb, column-major: host B in, host X out
+  // m functions per column (ensure_batch_multi), for this nb and kcap: mcols interleaved
+  // result vectors (ld x nb each, one per function) and the coefficient table (function f,
+  // column c at d_my + (f nb' + c) kcap for a group of nb' columns); nullptr: mcols == 0
+  double *d_mx = nullptr, *d_my = nullptr;
+  size_t mcols = 0;
+  double* d_mstage = nullptr;       // n x (nb mstage_cols), column-major: host X out
+  size_t mstage_cols = 0;
   BatchDev S{};
 };
 
@@ -229,6 +236,12 @@ void ensure_multi(tpl_op_s* op, size_t m);
 // (free_batch): the next batch call allocates for the new layout.
 void ensure_batch(tpl_op_s* op, int nb, size_t k);
 void free_batch(tpl_op_s* op);
+// The m result vectors and the coefficient table of a batch-multi group, for the batch
+// buffers' current nb and kcap (ensure_batch first), allocated on first use and counted
+// in device_bytes. They grow with m (growing drops the cached graphs); whatever frees or
+// regrows the batch buffers frees them (free_batch). stage: also the host-side staging
+// block of the n x (nb m) result.
+void ensure_batch_multi(tpl_op_s* op, size_t m, bool stage);
 double* ensure_view(tpl_op_s* op, size_t cols);
 // Per-step second-pass records of the selective re-orthogonalisation (slot j - 1: step j).
 int* reorth_records(const tpl_op_s* op);
@@ -294,6 +307,11 @@ void run_pass2_multi(tpl_op_s* op, size_t steps, size_t m);
 // two up to the group's largest steps_taken, one graph per (kmax, nb).
 void run_pass1_batch(tpl_op_s* op, size_t k, int nb);
 void run_pass2_batch(tpl_op_s* op, size_t kmax, int nb);
+// Pass two of a group for the m coefficient columns per right-hand side in op->bat.d_my
+// into op->bat.d_mx (ensure_batch_multi first). steps: the nb columns' steps_taken, as the
+// device state holds them. All equal (the normal case): one graph per (kmax, nb, m);
+// otherwise the launch list depends on every steps_c and runs uncaptured.
+void run_pass2_batch_multi(tpl_op_s* op, const size_t* steps, int nb, size_t m);
 void run_two_pass_dev(tpl_op_s* op, size_t k, int f);
 HostDecomp fetch_decomp(tpl_op_s* op);
 

@@ -342,7 +342,39 @@ void free_batch(tpl_op_s* op) {
   BatchBufs& b = op->bat;
   dev_free(op, b.d_vecs), dev_free(op, b.d_state), dev_free(op, b.d_P), dev_free(op, b.d_Pcnt);
   dev_free(op, b.d_stage);
+  dev_free(op, b.d_mx), dev_free(op, b.d_my), dev_free(op, b.d_mstage);
   b = BatchBufs{};
+}
+// Freed before they grow, as the basis is; sized for the batch buffers' nb and kcap.
+void ensure_batch_multi(tpl_op_s* op, size_t m, bool stage) {
+  BatchBufs& b = op->bat;
+  if (b.nb == 0 || m == 0)
+    fail(TPL_ERR_INVALID_ARGUMENT, "ensure_batch_multi: no batch buffers to size by");
+  const size_t w = (size_t)b.nb;
+  if (m > b.mcols || !b.d_mx) {
+    const size_t cols = std::max(m, b.mcols);
+    drop_graphs(op);
+    dev_free(op, b.d_mx), dev_free(op, b.d_my);
+    b.mcols = 0;
+    try {
+      dev_alloc(op, &b.d_mx, cols * (size_t)op->ld * w * sizeof(double));
+      HIPCHK(hipMemset(b.d_mx, 0, cols * (size_t)op->ld * w * sizeof(double)));
+      dev_alloc(op, &b.d_my, cols * w * b.kcap * sizeof(double));
+      HIPCHK(hipMemset(b.d_my, 0, cols * w * b.kcap * sizeof(double)));
+    } catch (...) {
+      dev_free(op, b.d_mx), dev_free(op, b.d_my);
+      throw;
+    }
+    b.mcols = cols;
+  }
+  if (stage && (m > b.mstage_cols || !b.d_mstage)) {
+    const size_t cols = std::max(m, b.mstage_cols);
+    dev_free(op, b.d_mstage);
+    b.mstage_cols = 0;
+    dev_alloc(op, &b.d_mstage,
+              std::max<size_t>((size_t)op->part.n, 1) * w * cols * sizeof(double));
+    b.mstage_cols = cols;
+  }
 }
 // Freed before they grow, as the basis is. State layout, per group: [flags: 8 int32 per
 // column] [norms nb (kc + 1)] [alphas nb kc] [betas nb kc] [y nb kc] | 64-B aligned:

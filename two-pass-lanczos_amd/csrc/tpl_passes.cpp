@@ -22,6 +22,8 @@ enum GraphKind {
   kGPass2Multi,       // pass two of a multi-function solve: one graph per (steps, m)
   kGPass1Batch,       // pass one of a batch group: one graph per (k, NB)
   kGPass2Batch,       // pass two of a batch group: one graph per (largest steps, NB)
+  kGPass2BatchMulti,  // pass two of a batch-multi group whose columns took the same
+                      // number of steps: one graph per (steps, NB, m)
 };
 // What tells one pass-one sequence (and its graph) from another, beside k: the basis is
 // stored (the standard pass), T_k's LU is eliminated as it goes (a device inv follows:
@@ -314,6 +316,52 @@ void run_pass1_batch(tpl_op_s* op, size_t k, int nb) {
 void run_pass2_batch(tpl_op_s* op, size_t kmax, int nb) {
   check_batch(op, kmax, nb);
   run_graph(op, kGPass2Batch, kmax * 8 + (size_t)nb, [&] { enqueue_pass2_batch(op, kmax, nb); });
+}
+
+// ---- m functions of every column of a group (tpl_lanczos_two_pass_batch_multi): the
+// group's pass two with every record's nflush 0 (bp2_coefs0), so bp2_spmv regenerates
+// v_{j+1} and leaves x alone, and after each step at which some column flushes bp2_xacc
+// applies the grouped flush to every function's group vector, kBatchMultiFuncs functions
+// per launch, from the three live ring vectors. The kernel takes each column's count from
+// the device-held steps_c; the host's copy only decides which launches are worth making.
+static void enqueue_pass2_batch_multi(tpl_op_s* op, const size_t* steps, int nb, size_t m) {
+  const CsrDev A = csr_dev(op);
+  BatchBufs& bb = op->bat;
+  const BatchDev& S = bb.S;
+  const int64_t xs = op->ld * nb;  // one function's group vector
+  size_t kmax = 0;
+  for (int c = 0; c < nb; ++c) kmax = std::max(kmax, steps[c]);
+  HIPCHK(launch::bp2_minit(nb, A, S, bb.d_my, (int)m, bb.b, bb.R[1], bb.d_mx, xs, op->stream));
+  HIPCHK(launch::bp2_coefs0(nb, S, (int)kmax, op->stream));
+  for (int j = 1; j < (int)kmax; ++j) {
+    double *vp = bb.R[(j + 2) % 3], *vc = bb.R[j % 3], *vn = bb.R[(j + 1) % 3];
+    HIPCHK(launch::bp2_spmv(nb, A, S, vc, j >= 2 ? vp : nullptr, vn, bb.x, j, op->stream));
+    bool any = false;
+    for (int c = 0; c < nb; ++c)
+      any = any || (j < (int)steps[c] && p2_flush(j, (int)steps[c] - 1) > 0);
+    if (!any) continue;
+    for (size_t f0 = 0; f0 < m; f0 += kBatchMultiFuncs)
+      HIPCHK(launch::bp2_xacc(nb, A, S, bb.d_my + f0 * (size_t)nb * bb.kcap, j, vp, vc, vn,
+                              bb.d_mx + f0 * (size_t)xs, xs,
+                              (int)std::min<size_t>(kBatchMultiFuncs, m - f0), op->stream));
+  }
+}
+void run_pass2_batch_multi(tpl_op_s* op, const size_t* steps, int nb, size_t m) {
+  size_t kmax = 0;
+  bool even = true;
+  for (int c = 0; c < nb; ++c) {
+    kmax = std::max(kmax, steps[c]);
+    even = even && steps[c] == steps[0];
+  }
+  check_batch(op, kmax, nb);
+  if (m == 0 || m > op->bat.mcols || m > TPL_MULTI_MAX)
+    fail(TPL_ERR_INVALID_ARGUMENT, "batch-multi group: buffers smaller than the request");
+  if (!even) {  // the launch list depends on every steps_c: not captured
+    enqueue_pass2_batch_multi(op, steps, nb, m);
+    return;
+  }
+  run_graph(op, kGPass2BatchMulti, (kmax * 8 + (size_t)nb) * (TPL_MULTI_MAX + 1) + m,
+            [&] { enqueue_pass2_batch_multi(op, steps, nb, m); });
 }
 
 // Copy flags | norms[0] | alphas | betas back (one D2H), synchronise.

@@ -393,10 +393,59 @@ std::vector<double> call_ftks(const tpl_ftk_fn* fs, void** f_users, size_t m,
   }
   return Y;
 }
-// The steps x m host table into the device table (columns ycap apart).
-void upload_y(tpl_op_s* op, const double* Y, size_t steps, size_t m) {
-  HIPCHK(hipMemcpy2DAsync(op->d_Y, op->ycap * sizeof(double), Y, steps * sizeof(double),
+// The steps x m host table (columns ldy apart) into the device table (columns ycap apart).
+void upload_y(tpl_op_s* op, const double* Y, size_t ldy, size_t steps, size_t m) {
+  HIPCHK(hipMemcpy2DAsync(op->d_Y, op->ycap * sizeof(double), Y, ldy * sizeof(double),
                           steps * sizeof(double), m, hipMemcpyHostToDevice, op->stream));
+}
+// tpl_lanczos_two_pass_multi after its argument checks.
+void two_pass_multi(tpl_op_s* op, const double* b, size_t k, const tpl_ftk_fn* fs, void** f_users,
+                    size_t m, double* x_out, int mem) {
+  // 1. pass one, once (the host-f path of tpl_lanczos_two_pass)
+  op->last_one_graph = false;
+  run_pass_one(op, b, k, mem, false, false);
+  const HostDecomp d = fetch_decomp(op);
+  if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+  if (d.steps == 0) {
+    zero_out_cols(op, x_out, m, mem);
+    return;
+  }
+  // 2. every f_i(T_k) e_1 on the host, 3. y_i = y'_i * ||b||
+  const std::vector<double> Y = call_ftks(fs, f_users, m, d, true);
+  ensure_multi(op, m);
+  upload_y(op, Y.data(), d.steps, d.steps, m);
+  // 4. one pass two for all of them
+  run_pass2_multi(op, d.steps, m);
+  download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+  sync_checked(op);
+}
+// tpl_lanczos_pass_two_multi after its argument checks (y's columns ldy apart).
+void pass_two_multi(tpl_op_s* op, const double* b, const double* alphas, size_t n_alphas,
+                    const double* betas, size_t n_betas, size_t steps, double b_norm,
+                    const double* y, size_t ldy, size_t m, double* x_out, int mem) {
+  if (b_norm <= kBreakdownTol)
+    fail_input("The initial vector `b` must not be a zero vector.");
+  if (steps == 0) {
+    zero_out_cols(op, x_out, m, mem);
+    return;
+  }
+  if (n_alphas < steps || n_betas + 1 < steps || !alphas || (steps > 1 && !betas) || !y)
+    fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
+  if (steps > (size_t)INT32_MAX / 2) fail(TPL_ERR_INVALID_ARGUMENT, "steps too large");
+  ensure_state(op, steps);
+  ensure_multi(op, m);
+  const DevState& S = op->st.S;
+  HIPCHK(hipMemcpyAsync(S.norms, &b_norm, sizeof(double), hipMemcpyHostToDevice, op->stream));
+  HIPCHK(hipMemcpyAsync(S.alphas, alphas, steps * sizeof(double), hipMemcpyHostToDevice,
+                        op->stream));
+  if (steps > 1)
+    HIPCHK(hipMemcpyAsync(S.betas, betas, (steps - 1) * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+  upload_y(op, y, ldy, steps, m);
+  upload_vec(op, op->b, b, mem);
+  run_pass2_multi(op, steps, m);
+  download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+  sync_checked(op);
 }
 } // namespace
 
@@ -410,23 +459,7 @@ tpl_status tpl_lanczos_two_pass_multi(tpl_op_t op, const double* b, int64_t b_le
     check_b(op, b, b_len);
     check_k(k);
     const TimingOff untimed(op);
-    // 1. pass one, once (the host-f path of tpl_lanczos_two_pass)
-    op->last_one_graph = false;
-    run_pass_one(op, b, k, mem, false, false);
-    const HostDecomp d = fetch_decomp(op);
-    if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
-    if (d.steps == 0) {
-      zero_out_cols(op, x_out, m, mem);
-      return;
-    }
-    // 2. every f_i(T_k) e_1 on the host, 3. y_i = y'_i * ||b||
-    const std::vector<double> Y = call_ftks(fs, f_users, m, d, true);
-    ensure_multi(op, m);
-    upload_y(op, Y.data(), d.steps, m);
-    // 4. one pass two for all of them
-    run_pass2_multi(op, d.steps, m);
-    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
-    sync_checked(op);
+    two_pass_multi(op, b, k, fs, f_users, m, x_out, mem);
   });
 }
 
@@ -469,29 +502,8 @@ tpl_status tpl_lanczos_pass_two_multi(tpl_op_t op, const double* b, int64_t b_le
     check_multi(op, x_out != nullptr, m);  // y may be NULL with steps == 0
     check_b(op, b, b_len);
     if (steps != y_len) fail_param_mismatch("y_k", steps, y_len);
-    if (b_norm <= kBreakdownTol)
-      fail_input("The initial vector `b` must not be a zero vector.");
-    if (steps == 0) {
-      zero_out_cols(op, x_out, m, mem);
-      return;
-    }
-    if (n_alphas < steps || n_betas + 1 < steps || !alphas || (steps > 1 && !betas) || !y)
-      fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
-    if (steps > (size_t)INT32_MAX / 2) fail(TPL_ERR_INVALID_ARGUMENT, "steps too large");
-    ensure_state(op, steps);
-    ensure_multi(op, m);
-    const DevState& S = op->st.S;
-    HIPCHK(hipMemcpyAsync(S.norms, &b_norm, sizeof(double), hipMemcpyHostToDevice, op->stream));
-    HIPCHK(hipMemcpyAsync(S.alphas, alphas, steps * sizeof(double), hipMemcpyHostToDevice,
-                          op->stream));
-    if (steps > 1)
-      HIPCHK(hipMemcpyAsync(S.betas, betas, (steps - 1) * sizeof(double), hipMemcpyHostToDevice,
-                            op->stream));
-    upload_y(op, y, steps, m);
-    upload_vec(op, op->b, b, mem);
-    run_pass2_multi(op, steps, m);
-    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
-    sync_checked(op);
+    pass_two_multi(op, b, alphas, n_alphas, betas, n_betas, steps, b_norm, y, steps, m, x_out,
+                   mem);
   });
 }
 
@@ -617,6 +629,39 @@ GroupHead pass_one_group(tpl_op_s* op, const double* B, size_t k, int nb, int me
   sync_checked(op);
   return g;
 }
+// tpl_lanczos_two_pass_batch after its argument checks.
+void two_pass_batch(tpl_op_s* op, const double* B, size_t s, size_t k, tpl_ftk_fn f, void* f_user,
+                    double* x_out, int mem) {
+  op->last_one_graph = false;
+  const size_t n = (size_t)op->part.n;
+  for (size_t c0 = 0; c0 < s;) {
+    const int nb = n == 0 ? 1 : group_width(s - c0);
+    if (nb == 1) {  // the single solve's host-f path
+      two_pass_host_f(op, B + c0 * n, k, f, f_user, x_out + c0 * n, mem, false);
+      ++c0;
+      continue;
+    }
+    // 1. pass one for the group's columns in lock-step
+    GroupHead g = pass_one_group(op, B + c0 * n, k, nb, mem);
+    // 2. f(T_k) e_1 per column on the host, in column order, 3. y_c = y'_c * ||b_c||
+    size_t kmax = 0;
+    std::vector<double> y;
+    for (int c = 0; c < nb; ++c) {
+      const HostDecomp d = g.decomp((size_t)c);
+      if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+      call_ftk(f, f_user, d, y);
+      for (size_t j = 0; j < d.steps; ++j) g.y((size_t)c)[j] = y[j] * d.b_norm;
+      kmax = std::max(kmax, d.steps);
+    }
+    HIPCHK(hipMemcpyAsync(op->bat.S.y, g.y(0), g.w * g.kc * sizeof(double),
+                          hipMemcpyHostToDevice, op->stream));
+    // 4. one pass two for all of them
+    run_pass2_batch(op, kmax, nb);
+    download_group(op, x_out + c0 * n, nb, mem);
+    sync_checked(op);
+    c0 += (size_t)nb;
+  }
+}
 } // namespace
 
 extern "C" {
@@ -629,35 +674,7 @@ tpl_status tpl_lanczos_two_pass_batch(tpl_op_t op, const double* B, int64_t b_le
     check_b(op, B, b_len);
     check_k(k);
     const TimingOff untimed(op);
-    op->last_one_graph = false;
-    const size_t n = (size_t)op->part.n;
-    for (size_t c0 = 0; c0 < s;) {
-      const int nb = n == 0 ? 1 : group_width(s - c0);
-      if (nb == 1) {  // the single solve's host-f path
-        two_pass_host_f(op, B + c0 * n, k, f, f_user, x_out + c0 * n, mem, false);
-        ++c0;
-        continue;
-      }
-      // 1. pass one for the group's columns in lock-step
-      GroupHead g = pass_one_group(op, B + c0 * n, k, nb, mem);
-      // 2. f(T_k) e_1 per column on the host, in column order, 3. y_c = y'_c * ||b_c||
-      size_t kmax = 0;
-      std::vector<double> y;
-      for (int c = 0; c < nb; ++c) {
-        const HostDecomp d = g.decomp((size_t)c);
-        if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
-        call_ftk(f, f_user, d, y);
-        for (size_t j = 0; j < d.steps; ++j) g.y((size_t)c)[j] = y[j] * d.b_norm;
-        kmax = std::max(kmax, d.steps);
-      }
-      HIPCHK(hipMemcpyAsync(op->bat.S.y, g.y(0), g.w * g.kc * sizeof(double),
-                            hipMemcpyHostToDevice, op->stream));
-      // 4. one pass two for all of them
-      run_pass2_batch(op, kmax, nb);
-      download_group(op, x_out + c0 * n, nb, mem);
-      sync_checked(op);
-      c0 += (size_t)nb;
-    }
+    two_pass_batch(op, B, s, k, f, f_user, x_out, mem);
   });
 }
 
@@ -733,6 +750,154 @@ tpl_status tpl_lanczos_pass_two_batch(tpl_op_t op, const double* B, int64_t b_le
       upload_group(op, B + c0 * n, nb, mem);
       run_pass2_batch(op, kmax, nb);
       download_group(op, x_out + c0 * n, nb, mem);
+      sync_checked(op);
+      c0 += (size_t)nb;
+    }
+  });
+}
+
+} // extern "C"
+
+// ---- f_i(A) b_c: m functions of s right-hand sides in one run ---------------------------
+namespace {
+// Every group of four or two columns runs fused (lock-step pass one, one pass two for the
+// group's nb x m results): both widths measured faster than nb multi-function solves and than
+// m batch solves (profiles/batch_multi_timing.txt), so no width is
+// routed to an existing path.
+void check_batch_multi_args(tpl_op_s* op, bool have_args, size_t s, size_t m) {
+  if (!op || !have_args) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (s == 0 || s > (size_t)TPL_BATCH_MAX)
+    fail(TPL_ERR_INVALID_ARGUMENT, "s must be between 1 and TPL_BATCH_MAX");
+  if (m == 0 || m > (size_t)TPL_MULTI_MAX)
+    fail(TPL_ERR_INVALID_ARGUMENT, "m must be between 1 and TPL_MULTI_MAX");
+  set_device(op);
+  if (op->dist) fail(TPL_ERR_UNSUPPORTED, "batch-multi solve of a partitioned operator");
+}
+// The group's coefficient table: function f, column c at (f nb + c) kcap.
+struct GroupY {
+  std::vector<double> h;
+  size_t nb, kc;
+  GroupY(const tpl_op_s* op, int nb_, size_t m) : nb((size_t)nb_), kc(op->bat.kcap) {
+    h.assign(m * nb * kc, 0.0);
+  }
+  double* col(size_t f, size_t c) { return h.data() + (f * nb + c) * kc; }
+  void upload(tpl_op_s* op) {
+    HIPCHK(hipMemcpyAsync(op->bat.d_my, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+  }
+};
+// The group's m interleaved result vectors out to the nb m columns (c m + f) of the caller's X.
+void download_group_multi(tpl_op_s* op, double* X, int nb, size_t m, int mem) {
+  const int64_t n = op->part.n;
+  double* dst = mem == TPL_MEM_DEVICE ? X : op->bat.d_mstage;
+  HIPCHK(launch::bm_deinterleave(nb, n, dst, op->bat.d_mx, op->ld * nb, (int)m, op->bufs.d_iperm,
+                                 op->stream));
+  if (mem != TPL_MEM_DEVICE && n > 0)
+    HIPCHK(hipMemcpyAsync(X, dst, (size_t)n * nb * m * sizeof(double), hipMemcpyDeviceToHost,
+                          op->stream));
+}
+} // namespace
+
+extern "C" {
+
+tpl_status tpl_lanczos_two_pass_batch_multi(tpl_op_t op, const double* B, int64_t b_len,
+                                            size_t s, size_t k, const tpl_ftk_fn* fs,
+                                            void** f_users, size_t m, double* x_out, int mem) {
+  return guarded([&] {
+    check_batch_multi_args(op, B && fs && x_out, s, m);
+    check_b(op, B, b_len);
+    check_k(k);
+    const TimingOff untimed(op);
+    if (m == 1) {  // one function: the batch solve
+      two_pass_batch(op, B, s, k, fs[0], f_users ? f_users[0] : nullptr, x_out, mem);
+      return;
+    }
+    op->last_one_graph = false;
+    const size_t n = (size_t)op->part.n;
+    for (size_t c0 = 0; c0 < s;) {
+      const int nb = n == 0 ? 1 : group_width(s - c0);
+      if (nb == 1) {  // the multi-function solve of that column
+        two_pass_multi(op, B + c0 * n, k, fs, f_users, m, x_out + c0 * m * n, mem);
+        ++c0;
+        continue;
+      }
+      // 1. pass one for the group's columns in lock-step
+      GroupHead g = pass_one_group(op, B + c0 * n, k, nb, mem);
+      ensure_batch_multi(op, m, mem != TPL_MEM_DEVICE);
+      // 2. per column in order: the zero-vector check, then every f_i(T_k) e_1 on the host
+      //    in index order, 3. y_{c,i} = y'_{c,i} * ||b_c||
+      GroupY Y(op, nb, m);
+      size_t steps[kBatchNbMax];
+      std::vector<double> y;
+      for (int c = 0; c < nb; ++c) {
+        const HostDecomp d = g.decomp((size_t)c);
+        if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+        for (size_t i = 0; i < m; ++i) {
+          call_ftk(fs[i], f_users ? f_users[i] : nullptr, d, y);
+          double* yc = Y.col(i, (size_t)c);
+          for (size_t j = 0; j < d.steps; ++j) yc[j] = y[j] * d.b_norm;
+        }
+        steps[c] = d.steps;
+      }
+      Y.upload(op);
+      // 4. one pass two for all nb x m results
+      run_pass2_batch_multi(op, steps, nb, m);
+      download_group_multi(op, x_out + c0 * m * n, nb, m, mem);
+      sync_checked(op);
+      c0 += (size_t)nb;
+    }
+  });
+}
+
+tpl_status tpl_lanczos_pass_two_batch_multi(tpl_op_t op, const double* B, int64_t b_len,
+                                            size_t s, const double* alphas, const double* betas,
+                                            size_t ld, const size_t* steps, const double* b_norms,
+                                            const double* y, size_t m, double* x_out, int mem) {
+  return guarded([&] {
+    check_batch_multi_args(op, B && x_out && steps && b_norms, s, m);
+    check_b(op, B, b_len);
+    const TimingOff untimed(op);
+    // the single call's checks, per column in ascending order
+    for (size_t c = 0; c < s; ++c) {
+      if (b_norms[c] <= kBreakdownTol)
+        fail_input("The initial vector `b` must not be a zero vector.");
+      if (steps[c] > ld || (steps[c] > 0 && (!alphas || !y)) || (steps[c] > 1 && !betas))
+        fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
+      if (steps[c] > (size_t)INT32_MAX / 2) fail(TPL_ERR_INVALID_ARGUMENT, "steps too large");
+    }
+    const size_t n = (size_t)op->part.n;
+    for (size_t c0 = 0; c0 < s;) {
+      const int nb = n == 0 ? 1 : group_width(s - c0);
+      if (nb == 1) {  // the multi-function pass two of that column
+        const size_t st = steps[c0];
+        auto col = [&](const double* p) { return p ? p + c0 * ld : nullptr; };
+        pass_two_multi(op, B + c0 * n, col(alphas), st, col(betas), st > 0 ? st - 1 : 0, st,
+                       b_norms[c0], y ? y + c0 * m * ld : nullptr, ld, m, x_out + c0 * m * n, mem);
+        ++c0;
+        continue;
+      }
+      size_t kmax = 1;
+      for (int c = 0; c < nb; ++c) kmax = std::max(kmax, steps[c0 + c]);
+      ensure_batch(op, nb, kmax);
+      ensure_batch_multi(op, m, mem != TPL_MEM_DEVICE);
+      // decompositions -> the group's state (steps_c, ||b_c||, alphas, betas), y -> the table
+      GroupHead g(op);
+      GroupY Y(op, nb, m);
+      for (int c = 0; c < nb; ++c) {
+        const size_t cc = c0 + (size_t)c, st = steps[cc];
+        g.flags((size_t)c)[2] = (int32_t)st;
+        g.norms((size_t)c)[0] = b_norms[cc];
+        if (st > 0) std::memcpy(g.alphas((size_t)c), alphas + cc * ld, st * sizeof(double));
+        if (st > 1) std::memcpy(g.betas((size_t)c), betas + cc * ld, (st - 1) * sizeof(double));
+        for (size_t i = 0; i < m && st > 0; ++i)
+          std::memcpy(Y.col(i, (size_t)c), y + (cc * m + i) * ld, st * sizeof(double));
+      }
+      HIPCHK(hipMemcpyAsync(op->bat.d_state, g.h.data(), g.h.size() * sizeof(double),
+                            hipMemcpyHostToDevice, op->stream));
+      Y.upload(op);
+      upload_group(op, B + c0 * n, nb, mem);
+      run_pass2_batch_multi(op, steps + c0, nb, m);
+      download_group_multi(op, x_out + c0 * m * n, nb, m, mem);
       sync_checked(op);
       c0 += (size_t)nb;
     }

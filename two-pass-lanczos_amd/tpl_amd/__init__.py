@@ -14,13 +14,13 @@ from . import algorithms, error, ftk, solvers
 from .error import DataLoaderError, LanczosError, LanczosErrorKind, TplError
 from .operator import HipCsrOp, HostPlan, device_count, locality_order, refresh_uploaded
 from .solvers import (lanczos, lanczos_multi, lanczos_two_pass, lanczos_two_pass_batch,
-                      lanczos_two_pass_multi)
+                      lanczos_two_pass_batch_multi, lanczos_two_pass_multi)
 
 __version__ = "0.1.0"
 LIB_PATH = _lib.LIB_PATH
 
 __all__ = [
-    "lanczos", "lanczos_two_pass", "lanczos_multi", "lanczos_two_pass_multi", "lanczos_two_pass_batch", "algorithms", "solvers", "error", "ftk", "HipCsrOp",
+    "lanczos", "lanczos_two_pass", "lanczos_multi", "lanczos_two_pass_multi", "lanczos_two_pass_batch", "lanczos_two_pass_batch_multi", "algorithms", "solvers", "error", "ftk", "HipCsrOp",
     "LanczosError", "LanczosErrorKind", "TplError", "DataLoaderError", "device_count",
     "locality_order", "HostPlan", "refresh_uploaded",
 ]

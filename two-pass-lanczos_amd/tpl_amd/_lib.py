@@ -120,6 +120,14 @@ tpl_lanczos_pass_one_batch = _sig("tpl_lanczos_pass_one_batch", c_int, c_void_p,
 tpl_lanczos_pass_two_batch = _sig("tpl_lanczos_pass_two_batch", c_int, c_void_p, c_void_p, c_int64,
                                   c_size_t, PD, PD, c_size_t, POINTER(c_size_t), PD, PD, c_void_p,
                                   c_int)
+# functions per k_bp2_xacc launch (csrc/tpl_batch.h kBatchMultiFuncs): more run as further launches
+BATCH_MULTI_FUNCS = 4
+tpl_lanczos_two_pass_batch_multi = _sig("tpl_lanczos_two_pass_batch_multi", c_int, c_void_p,
+                                        c_void_p, c_int64, c_size_t, c_size_t, POINTER(c_void_p),
+                                        POINTER(c_void_p), c_size_t, c_void_p, c_int)
+tpl_lanczos_pass_two_batch_multi = _sig("tpl_lanczos_pass_two_batch_multi", c_int, c_void_p,
+                                        c_void_p, c_int64, c_size_t, PD, PD, c_size_t,
+                                        POINTER(c_size_t), PD, PD, c_size_t, c_void_p, c_int)
 tpl_load_kkt_system = _sig("tpl_load_kkt_system", c_int, c_char_p, c_char_p, POINTER(CsrHost))
 tpl_csr_host_free = _sig("tpl_csr_host_free", None, POINTER(CsrHost))
 tpl_generate_kkt = _sig("tpl_generate_kkt", c_int, c_int64, c_int64, ctypes.c_uint64,
@@ -239,6 +247,7 @@ EXPORTED += ["tpl_plan_create"]
 EXPORTED += ["tpl_lanczos_two_pass_multi", "tpl_lanczos_multi", "tpl_lanczos_pass_two_multi"]
 EXPORTED += ["tpl_lanczos_two_pass_batch", "tpl_lanczos_pass_one_batch",
              "tpl_lanczos_pass_two_batch"]
+EXPORTED += ["tpl_lanczos_two_pass_batch_multi", "tpl_lanczos_pass_two_batch_multi"]
 EXPORTED += ["tpl_dist_op_create_replicated", "tpl_op_local_rows", "tpl_dist_partition", "tpl_dist_unique_id", "tpl_dist_create",
              "tpl_dist_create_host", "tpl_dist_destroy", "tpl_dist_op_create_csr",
              "tpl_dist_op_create_halo", "tpl_dist_choose_partition", "tpl_dist_op_create_auto",

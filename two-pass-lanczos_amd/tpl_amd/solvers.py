@@ -20,6 +20,11 @@ the single solve with ``f_tk_solvers[i]`` evaluated on the host.
 f(A) b_1 ... f(A) b_s for the columns of ``B`` in one lock-step two-pass run. It returns shape
 (n, s) with strides (1, n) — column c is bitwise the single solve of ``B[:, c]`` with
 ``f_tk_solver`` evaluated on the host.
+
+``lanczos_two_pass_batch_multi(operator, B, k, f_tk_solvers)`` (no reference counterpart) has
+both axes: f_i(A) b_c for m functions and the s columns of ``B`` in one run. It returns shape
+(n, m, s) with strides (1, n, n m) — ``X[:, i, c]`` is bitwise the single solve of ``B[:, c]``
+with ``f_tk_solvers[i]`` evaluated on the host.
 """
 from __future__ import annotations
 
@@ -101,3 +106,31 @@ def lanczos_two_pass_batch(operator, B, k: int, f_tk_solver):
     except LanczosError as e:
         raise ftk.remap_error(e, keep) from None
     return x.T
+
+
+def lanczos_two_pass_batch_multi(operator, B, k: int, f_tk_solvers):
+    """f_i(A) b_c for every solver i and every column c of ``B`` (n x s) by ONE run: per group
+    of columns pass one in lock-step, every f_i(T_k) on the host (column by column, the
+    solvers in index order), one pass two that regenerates the group's bases once for all
+    its results. Returns shape (n, m, s): ``X[:, i, c]`` = f_i(A) ``B[:, c]``."""
+    fs = list(f_tk_solvers)
+    if not fs:
+        raise ValueError("f_tk_solvers must hold at least one solver")
+    bv = Cols(B)
+    bv.check_rows(operator)
+    operator = as_operator(operator)
+    m = len(fs)
+    x = bv.empty(bv.s, m, bv.n)  # C-order (s, m, n) == column-major n x (s m), column c m + i
+    resolved = [ftk.resolve(f) for f in fs]
+    fptrs = (ctypes.c_void_p * m)(*[p for p, _ in resolved])
+    try:
+        check(_lib.tpl_lanczos_two_pass_batch_multi(operator.handle, bv.ptr, bv.n, bv.s, k, fptrs,
+                                                    None, m, Vec.ptr_of(x), bv.mem))
+    except LanczosError as e:
+        # as _run_multi: the first failure ends the call, so a solver that recorded a
+        # column-count mismatch is the one that failed
+        for _, keep in resolved:
+            if keep is not None and keep.mismatch is not None:
+                raise ftk.remap_error(e, keep) from None
+        raise
+    return x.permute(2, 1, 0) if hasattr(x, "permute") else x.transpose(2, 1, 0)
