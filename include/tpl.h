@@ -111,7 +111,9 @@ int64_t tpl_op_nnz(tpl_op_t op);
  * rank's own short rows are in that order and tpl_op_local_rows, not
  * tpl_op_permutation, reports it), bit 7: a replicated-long-row partition whose ranks
  * all-gather their norm partials and reduce them inside pass one's SpMV (no rank-total
- * launch). -1 if op is NULL.                                         */
+ * launch), bit 8: the last pass two the operator ran read long rows' sums
+ * from the long-row cache (tpl_op_set_long_cache: a tpl_lanczos_two_pass with the cache on;
+ * any other entry point's pass two reads 0). -1 if op is NULL.                         */
 int tpl_op_flags(tpl_op_t op);
 /* Locality order (single-GPU operators; rebuilds the layout). mode 1: the device
  * holds P A P^T, the short rows sorted by the long rows (hub columns) they reference
@@ -323,6 +325,30 @@ tpl_status tpl_lanczos_pass_two_batch_multi(tpl_op_t op, const double* B, int64_
  *        T_k that is not finite or whose spectrum is too wide for the expansion is handed
  *        back to the host solver inside the same call.                              */
 tpl_status tpl_op_set_device_ftk(tpl_op_t op, int mode);
+/* The long-row cache of tpl_lanczos_two_pass (single-GPU operators).
+ * Pass two regenerates pass one's basis bit for bit, so the sum (A v_j)_r of a long row r
+ * is the one pass one formed at its step j: pass one keeps these sums (n_long doubles per
+ * step) and pass two's steps read them back instead of gathering the long rows again.
+ * Results are bitwise the same with the cache on or off.
+ *   mode 0: off; 1: on, at most budget_bytes of device memory; 2 (default): on with the
+ *   default budget, two vectors' bytes (tpl_long_cache_default_budget), which keeps the
+ *   two-pass footprint O(n).
+ * The cache holds rows = min(kcap, budget / (8 n_long)) steps (tpl_long_cache_rows), kcap
+ * the solver state's capacity; pass-two steps past `rows` run the full step kernel. It is
+ * allocated with the solver state (a refused allocation leaves the operator as it was),
+ * counted by tpl_op_device_bytes (rows x n_long x 8 bytes; plus 4 n_long for the long rows'
+ * indices unless they are the operator's last rows, as the locality order puts them), and
+ * not kept when the operator has no long rows. Only tpl_lanczos_two_pass uses it: the stand-alone
+ * passes, the multi-function and batch solves and partitioned operators never do.
+ * Changing the mode or budget drops the cached graphs; the buffer is resized at the next
+ * solve. tpl_op_flags bit 8 tells whether the last pass two read the cache.            */
+tpl_status tpl_op_set_long_cache(tpl_op_t op, int mode, uint64_t budget_bytes);
+/* Host arithmetic of the above: the default budget for n rows (2 x 8 x n padded to the
+ * vector stride, a multiple of 64), and the steps cached under (mode, budget_bytes) for an
+ * n-row operator with n_long long rows and a state capacity of kcap steps.              */
+uint64_t tpl_long_cache_default_budget(int64_t n);
+uint64_t tpl_long_cache_rows(int mode, uint64_t budget_bytes, int64_t n, int64_t n_long,
+                             uint64_t kcap);
 /* Test / introspection: evaluate the device f(T_k) kernel alone on a given T_k (which 0:
  * inv, 1: exp; n alphas, n - 1 betas) into y_out (n host doubles, y' = f(T_k) e_1).
  * *on_device = 0 when the exp kernel handed the case back to the host (y_out then 0).  */

@@ -315,6 +315,11 @@ class HipCsrOp {
     detail::check(tpl_op_apply(op_, x.data(), y.data(), TPL_MEM_HOST));
     return y;
   }
+  // The long-row cache of lanczos_two_pass (tpl_op_set_long_cache): 0 off, 1 on with at
+  // most budget_bytes, 2 auto (default). Results are bitwise the same either way.
+  void set_long_cache(int mode, uint64_t budget_bytes = 0) {
+    detail::check(tpl_op_set_long_cache(op_, mode, budget_bytes));
+  }
   tpl_op_t handle() const { return op_; }
 
  private:

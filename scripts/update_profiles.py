@@ -28,7 +28,10 @@ with open(os.path.join(prof, f"{tag}_bench.json"), "w") as f:
 # the headline instance of k_p2_spmv: template variant 122 (500k KKT layout: uniform
 # width 2, int8 values, uint16 chunk and bin columns, chunk window); the other configs of
 # the same bench run (5k, 50k, 5M) instantiate other variants or share it with fewer calls
-HEADLINE = sys.argv[2] if len(sys.argv) > 2 else "k_p2_spmv<58>"
+# With the long-row cache (the default) every pass-two step of the headline runs
+# k_p2_cached<26> instead (the same format bits without the bins' column format): the
+# pass-two entries below are then that kernel's, and `kernel` / `pass_two_step_kernel` say so.
+P2_FULL, P2_CACHED = "k_p2_spmv<58>", "k_p2_cached<26>"
 blocks, cur = {}, None
 for l in open(os.path.join(out, "pmc_summary.txt")):
     if not l.startswith(" "):
@@ -46,8 +49,9 @@ def traffic(vals):
     return round(2 * vals["FETCH_SIZE"] * 1024 + vals["WRITE_SIZE"] * 1024)
 
 
+HEADLINE = sys.argv[2] if len(sys.argv) > 2 else (P2_CACHED if P2_CACHED in blocks else P2_FULL)
 vals = blocks[HEADLINE]
-d = {"kernel": "k_p2_spmv", "config": CFG,
+d = {"kernel": HEADLINE.split("<")[0], "config": CFG,
      "FETCH_SIZE_KiB": vals["FETCH_SIZE"], "WRITE_SIZE_KiB": vals["WRITE_SIZE"],
      "traffic_bytes_per_launch": traffic(vals),
      "correction": "2 x FETCH_SIZE (gfx950 half-count of wide reads) + WRITE_SIZE",
@@ -71,22 +75,32 @@ stats = {}
 import csv
 with open(os.path.join(out, "prof", "run_kernel_stats.csv")) as f:
     for r in csv.DictReader(f):
-        m = re.search(r"tpl::(k_p[12]_spmv|k_p1_axpy)(<\d+>)", r["Name"])
-        if m and m.group(1) + m.group(2) in ("k_p1_spmv<58>", "k_p2_spmv<58>", "k_p1_axpy<12>"):
+        m = re.search(r"tpl::(k_p[12]_spmv|k_p1_axpy|k_p2_cached)(<\d+>)", r["Name"])
+        if m and m.group(1) + m.group(2) in ("k_p1_spmv<58>", P2_FULL, P2_CACHED, "k_p1_axpy<12>"):
             stats[m.group(1)] = {"avg_ns": float(r["AverageNs"]), "calls": int(r["Calls"]),
                                  "percentage": float(r["Percentage"])}
+# bench.py reads the pass-two step under "k_p2_spmv": when the headline ran no full step,
+# that entry is the cached step's (it no longer performs the long rows' product, so B_spmv
+# over its time is not an SpMV bandwidth figure: DESIGN.md §6)
+p2_kernel = "k_p2_spmv"
+if "k_p2_cached" in stats and "k_p2_spmv" not in stats:
+    stats["k_p2_spmv"] = stats["k_p2_cached"]
+    p2_kernel = "k_p2_cached"
 med = {}
 mpath = os.path.join(prof, f"{tag}_kernel_medians.json")
 if os.path.exists(mpath):
     for name, v in json.load(open(mpath)).items():
-        for k in ("k_p1_spmv<58>", "k_p2_spmv<58>", "k_p1_axpy<12>"):
+        for k in ("k_p1_spmv<58>", P2_FULL, P2_CACHED, "k_p1_axpy<12>"):
             if name == k:
                 med[k.split("<")[0]] = round(1000.0 * v["median_us"], 1)
+    if p2_kernel == "k_p2_cached" and "k_p2_cached" in med:
+        med["k_p2_spmv"] = med["k_p2_cached"]
 sys.path.insert(0, ROOT)
 from bench import kernel_src_digest  # noqa: E402  (the profile's kernels: this tree's)
 bline = json.loads(line)
 b_spmv = (bline.get("roofline_live") or bline["roofline"])["bytes_per_launch"]
 rj = {"config": CFG, "kernel_src_sha16": kernel_src_digest(),
+      "pass_two_step_kernel": p2_kernel,  # whose figures the "k_p2_spmv" entries hold
       "bytes_per_launch": b_spmv,  # SURVEY §8(d) B_spmv of the headline (the bench line's)
       "avg_ns": {k: v["avg_ns"] for k, v in stats.items()}, "median_ns": med,
       "calls": {k: v["calls"] for k, v in stats.items()},

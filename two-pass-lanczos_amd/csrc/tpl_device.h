@@ -167,7 +167,9 @@ struct CsrDev {
   // Replicated-long-row partition (tpl_operator.cpp csr_dev, "hybrid"): the SpMV stores each
   // long row's rank-local partial in ypart[ri] instead of finishing the row, and the
   // norm partials cover elements [0, norm_n) only (replicated entries count once).
-  double* ypart;            // n_long partials of this rank (own slice of the all-gather)
+  double* ypart;            // n_long partials of this rank (own slice of the all-gather).
+                            // One GPU, k_p1_spmv only: the step's row of the long-row cache
+                            // (every long row's sum is also stored there), or nullptr
   int32_t long_defer;       // 1: long rows deferred to k_long_epi_*
   int32_t y_ld;             // stride of the all-gathered segments. Pass one: n_long
                             // partials + the rank's short-chunk alpha partials
@@ -276,7 +278,9 @@ struct P1SpmvArgs {
   int32_t long_defer;
   double* P;
   unsigned int* Pcnt;
-  double* ypart;
+  double* ypart;            // non-null: the long rows' sums are stored there (long_defer: and
+                            // the rows stop there) — the partition's segment, or the step's
+                            // row of the long-row cache
 };
 // The CsrDev fields P1SpmvArgs carries, under the same names: the launcher copies them in
 // (tpl::launch::p1_spmv), the kernel's CsrDev view copies them back (layout_of). A field

@@ -149,6 +149,14 @@ __device__ __forceinline__ void keep(double& v) { asm volatile("" : "+v"(v)); }
 // pre(i) loads the row's own vector entries (issued early); apply(i, s, pre, acc)
 // finishes the row given its SpMV sum s (acc: the thread's alpha accumulator).
 struct PreNone {};
+// long_y(A, ri, y): a long row's finished sum y, before its epilogue; true: the row stops
+// there. Partitioned (long_defer): y is this rank's part of the row, kept in ypart for the
+// exchange (k_long_epi_*).
+__device__ __forceinline__ bool defer_long_y(const CsrDev& A, int ri, double y) {
+  if (!A.long_defer) return false;
+  A.ypart[ri] = y;
+  return true;
+}
 struct EpiSpmv {
   double* y;
   __device__ __forceinline__ PreNone pre(int) const { return {}; }
@@ -157,6 +165,9 @@ struct EpiSpmv {
     return s;
   }
   __device__ __forceinline__ void long_alpha(int, double) const {}
+  __device__ __forceinline__ bool long_y(const CsrDev& A, int ri, double y) const {
+    return defer_long_y(A, ri, y);
+  }
 };
 
 // pass one / standard: w = y - beta_{j-1} v_{j-1}; alpha partial += v_j . w
@@ -174,6 +185,18 @@ struct EpiPass1 {
   __device__ __forceinline__ Pre1 pre(int i) const { return Pre1{r_cur[i], r_prev[i]}; }
   // long row r: its alpha partial is the single rounded product v * w
   __device__ __forceinline__ void long_alpha(int r, double acc) const { st_out(Pa_long + r, acc); }
+  // Pass one keeps the sum wherever ypart points: the partition's part of the row (and
+  // long_defer stops the row), or, on one GPU, this step's row of the long-row cache — pass
+  // two forms the same sum from the same operands in the same order, so a cached step
+  // (k_p2_cached) reads it back instead. nullptr: nothing kept. The reader is a later
+  // kernel, so any store would do; write-through (st_out) leaves the L2 during the kernel,
+  // a plain store as dirty lines at the boundary (same box, alternated four times: pass one
+  // 9.82-9.97 vs 10.06-10.08 us per step, the parent 9.88-10.08; solve 6.93 vs 7.01 ms).
+  __device__ __forceinline__ bool long_y(const CsrDev& A, int ri, double y) const {
+    double* yp = A.ypart;
+    if (yp) st_out(yp + ri, y);
+    return A.long_defer != 0;
+  }
   // returns v_j[i]
   __device__ __forceinline__ double apply(int i, double s, const Pre1& p, double& acc) const {
     const double v = p.rc * invN_cur;
@@ -252,6 +275,9 @@ struct EpiPass2R {
     return vn;
   }
   __device__ __forceinline__ void long_alpha(int, double) const {}
+  __device__ __forceinline__ bool long_y(const CsrDev& A, int ri, double y) const {
+    return defer_long_y(A, ri, y);
+  }
 };
 
 // Kernel-argument fields both paths of an SpMV-shaped kernel read, pinned in SGPRs at
@@ -677,10 +703,7 @@ __device__ __forceinline__ void long_bin(const CsrDev& A, int m, int s,
   // (0 + p, then + 0.0 for the other slots, which changes no bit): no hand-off.
   if (ns == 1 || sg.pad == 0) {
     const double y = 0.0 + p;
-    if (A.long_defer) {
-      A.ypart[sg.ri] = y;
-      return;
-    }
+    if (epi.long_y(A, sg.ri, y)) return;
     double acc = 0.0;
     epi.apply(sg.row, y, pre, acc);
     epi.long_alpha(sg.ri, acc);
@@ -732,10 +755,7 @@ __device__ __forceinline__ void long_bin(const CsrDev& A, int m, int s,
 #pragma unroll
   for (int k = 0; k < kSlices; ++k)
     if (k < ns) y = y + __longlong_as_double((long long)v[k]);
-  if (A.long_defer) {  // partitioned: this rank's part of the row; finished after the exchange
-    A.ypart[sg.ri] = y;
-    return;
-  }
+  if (epi.long_y(A, sg.ri, y)) return;  // partitioned: finished after the exchange
   double acc = 0.0;
   epi.apply(sg.row, y, pre, acc);
   epi.long_alpha(sg.ri, acc);

@@ -7,6 +7,8 @@
 //                       k_p2_init, k_p2_coefs, k_p2_spmv, k_p2_tail, k_gemv_recon.
 //                       k_ftk_inv stays beside k_p1_axpy: both inline lu_row, and apart
 //                       k_p1_axpy's elimination branch compiles to other registers
+//   tpl_k_p2_cached.hip k_p2_cached (the two-pass solver's pass-two step whose long rows read
+//                       the sums its pass one kept: the long-row cache)
 //   tpl_k_spmv.hip      k_spmv (the plain product), k_permute
 //   tpl_k_p1_gp.hip     k_p1_spmv_gp   } the pass-one SpMV for gathered / for more than 256
 //   tpl_k_p1_wide.hip   k_p1_spmv_wide } norm partials: partitioned and very large operators

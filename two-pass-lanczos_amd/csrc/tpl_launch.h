@@ -28,6 +28,13 @@ hipError_t p2_init(int64_t n, const DevState& S, const double* b, double* v1, do
 hipError_t p2_spmv(const CsrDev& A, const DevState& S, const double* xsrc, const double* v_cur,
                    const double* v_prev, double* v_next, double* x, double* Vcol, int j,
                    int nflush, hipStream_t s);
+// the same step with the long rows' sums read from `ycache`, the step's row of the long-row
+// cache (k_p2_cached, tpl_k_p2_cached.hip); needs n_long > 0. lrow: the long rows' row
+// indices, or nullptr when they are the last rows
+hipError_t p2_cached(const CsrDev& A, const DevState& S, const double* xsrc, const double* v_cur,
+                     const double* v_prev, double* v_next, double* x, double* Vcol,
+                     const double* ycache, const int32_t* lrow, int j, int nflush,
+                     hipStream_t s);
 // pass-two step records (EpiPass2R) for steps 1 .. k-1; dyn: activity from the device count
 hipError_t p2_coefs(const DevState& S, int k, int dyn, hipStream_t s);
 hipError_t gemv_recon(int64_t n, int steps, const DevState& S, const double* V, double* x,

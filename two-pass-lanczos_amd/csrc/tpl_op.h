@@ -78,6 +78,14 @@ struct SolverState {
   void* h_state = nullptr;  // pinned mirror of flags | norms | alphas | betas
   DevState S{};
   double* d_Pr = nullptr;   // reorthogonalisation partials (G * kcap)
+  // Long-row cache (tpl_op_set_long_cache): yrows x n_long doubles, zeroed; row j - 1 holds
+  // the long rows' sums (A v_j)_r of pass-one step j of the last tpl_lanczos_two_pass.
+  // nullptr: yrows == 0
+  double* d_ycache = nullptr;
+  size_t yrows = 0;
+  // the long rows' row indices, behind the sums in d_ycache's allocation; nullptr: the long
+  // rows are the last rows (Layout::s_identity)
+  int32_t* d_ylrow = nullptr;
 };
 
 // The buffers of a lock-step batch group (ensure_batch), for groups of nb columns and
@@ -176,6 +184,14 @@ struct tpl_op_s {
   bool timing = false;
   int device_ftk = 2;               // built-in inv on the device (one graph): 0 off, 1 on, 2 auto
   bool last_one_graph = false;      // the last tpl_lanczos_two_pass ran as one device graph
+  // long-row cache: 0 off, 1 on within long_cache_budget bytes, 2 auto (the default budget)
+  int long_cache = 2;
+  uint64_t long_cache_budget = 0;
+  // set by tpl_lanczos_two_pass for the length of the call (LongCacheScope): its pass one
+  // stores the cache rows and its pass two reads them. Every other entry point leaves it
+  // false and runs today's kernels
+  bool use_long_cache = false;
+  bool last_long_cache = false;     // the last tpl_lanczos_two_pass's pass two read the cache
   int64_t reorth_second = 0;        // second Gram-Schmidt passes of the last reorth solve
   // locality order (single GPU, tpl_op_set_reorder): the device works on P A P^T; vectors
   // cross the boundary through a gather (internal i <- caller's perm[i], back via iperm).
@@ -225,6 +241,14 @@ uint64_t device_bytes(const tpl_op_s* op);
 
 void rebuild_schedule(tpl_op_s* op, const SchedParams& cand, int reorder);
 void ensure_state(tpl_op_s* op, size_t k, bool reorth = false);
+// The long-row cache's budget rule (tpl_op_set_long_cache): steps cached for an operator of
+// n rows, n_long of them long, whose state holds kcap steps.
+uint64_t long_cache_default_budget(int64_t n);
+uint64_t long_cache_rows(int mode, uint64_t budget_bytes, int64_t n, int64_t n_long, uint64_t kcap);
+// Steps the operator's cache holds for the running tpl_lanczos_two_pass (0: not in use).
+inline size_t long_cache_steps(const tpl_op_s* op) {
+  return op->use_long_cache ? op->st.yrows : 0;
+}
 void ensure_basis(tpl_op_s* op, size_t cols);
 // The m result vectors and the m x kcap coefficient table of a multi-function solve, for
 // the state's current kcap (ensure_state first). They grow with m and kcap; growing drops
@@ -292,7 +316,8 @@ GraphExec capture_graph(tpl_op_s* op, const std::function<void()>& enqueue);
 void enqueue_reorth(tpl_op_s* op, int j, int mode);
 void enqueue_p1_prologue(tpl_op_s* op);
 void enqueue_p1_step(tpl_op_s* op, int j, int k, double* Vcol, bool elim = false,
-                     unsigned long long* st1 = nullptr, unsigned long long* st2 = nullptr);
+                     unsigned long long* st1 = nullptr, unsigned long long* st2 = nullptr,
+                     double* ycrow = nullptr);
 void launch_p2_step(tpl_op_s* op, const CsrDev& A, int j, int t, int nflush, double* Vcol);
 void enqueue_pass2(tpl_op_s* op, size_t steps, double* Vout);
 void enqueue_ftk_only(tpl_op_s* op, size_t k, int f, int scale);

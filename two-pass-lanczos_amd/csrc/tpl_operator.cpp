@@ -150,7 +150,7 @@ void upload_layout(tpl_op_s* op, const Layout& L, const std::vector<int32_t>& pe
 }
 
 void free_state(tpl_op_s* op, SolverState& s) {
-  dev_free(op, s.d_state), dev_free(op, s.d_Pr);
+  dev_free(op, s.d_state), dev_free(op, s.d_Pr), dev_free(op, s.d_ycache);
   if (s.h_state) hipHostFree(s.h_state);
   s = SolverState{};
 }
@@ -250,14 +250,64 @@ void rebuild_schedule(tpl_op_s* op, const SchedParams& cand, int reorder) {
   free_batch(op);
 }
 
+// ---- long-row cache (tpl_op_set_long_cache) ----------------------------------------------
+// Default budget: two vectors' bytes, so the two-pass footprint stays O(n): at most 12
+// vectors instead of 10.
+uint64_t long_cache_default_budget(int64_t n) { return 2 * 8 * (uint64_t)padded_stride(n); }
+uint64_t long_cache_rows(int mode, uint64_t budget_bytes, int64_t n, int64_t n_long, uint64_t kcap) {
+  if (mode == 0 || n_long <= 0) return 0;
+  const uint64_t budget = mode == 1 ? budget_bytes : long_cache_default_budget(n);
+  return std::min<uint64_t>(kcap, budget / (8 * (uint64_t)n_long));
+}
+namespace {
+// Steps the operator's cache should hold at a state capacity of kc steps. No cache for a
+// partitioned operator (its ypart is the exchange's).
+size_t wanted_cache_rows(const tpl_op_s* op, size_t kc) {
+  if (op->dist) return 0;
+  return (size_t)long_cache_rows(op->long_cache, op->long_cache_budget, op->part.n,
+                                 (int64_t)op->lay.lrows.size(), kc);
+}
+// A zeroed cache of `rows` steps into s (a one-graph solve's inactive launches read rows
+// no pass one wrote). Unless the long rows are the last rows (s_identity: long row l is row
+// n - n_long + l), their row indices follow the sums in the same allocation.
+void alloc_cache(tpl_op_s* op, SolverState& s, size_t rows) {
+  if (rows == 0) return;
+  const std::vector<int32_t>& lr = op->lay.lrows;
+  const size_t sums = rows * lr.size() * sizeof(double);
+  const size_t table = op->lay.s_identity ? 0 : (lr.size() * sizeof(int32_t) + 7) / 8 * 8;
+  dev_alloc(op, &s.d_ycache, sums + table);
+  HIPCHK(hipMemset(s.d_ycache, 0, sums));
+  if (table) {
+    s.d_ylrow = reinterpret_cast<int32_t*>(s.d_ycache + rows * lr.size());
+    HIPCHK(hipMemcpy(s.d_ylrow, lr.data(), lr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  s.yrows = rows;
+}
+} // namespace
+
 // state layout: [flags: 8 int32 (kFlagBytes)] [norms kcap+1] [alphas kcap] [betas kcap] [y kcap]
 // [Pa NA] [Pb G2] [p2c 8 kcap] [lu 4 kcap + 3]; reorthogonalisation partials separately (d_Pr).
 // A larger state is built aside and swapped in once it is complete (as rebuild_schedule
 // does the layout): when an allocation throws, the operator keeps its state, its kcap and
 // its graphs, and what was allocated on the way is freed. The price: while both blocks
 // exist the peak device memory is one state block higher (about 20 k doubles plus the
-// partial arrays).
+// partial arrays). The long-row cache is part of the state: sized with it, built aside with
+// it, and rebuilt alone (the same way) when only its mode or budget changed.
 void ensure_state(tpl_op_s* op, size_t k, bool reorth) {
+  if (k <= op->st.kcap && wanted_cache_rows(op, op->st.kcap) != op->st.yrows) {
+    SolverState ns;  // carries the new cache only; after the swap below, the old one
+    try {
+      alloc_cache(op, ns, wanted_cache_rows(op, op->st.kcap));
+    } catch (...) {
+      dev_free(op, ns.d_ycache);
+      throw;
+    }
+    std::swap(op->st.d_ycache, ns.d_ycache);
+    std::swap(op->st.d_ylrow, ns.d_ylrow);
+    std::swap(op->st.yrows, ns.yrows);
+    dev_free(op, ns.d_ycache);
+    drop_graphs(op);
+  }
   if (k > op->st.kcap) {
     const size_t kc = std::max<size_t>(k, 16);
     const CsrDev A = csr_dev(op);
@@ -273,6 +323,7 @@ void ensure_state(tpl_op_s* op, size_t k, bool reorth) {
       HIPCHK(hipMemset(ns.d_state, 0, bytes));
       HIPCHK(hipHostMalloc(&ns.h_state, kFlagBytes + (4 * kc + 1) * sizeof(double),
                            hipHostMallocDefault));
+      alloc_cache(op, ns, wanted_cache_rows(op, kc));
     } catch (...) {
       free_state(op, ns);
       throw;
@@ -697,7 +748,26 @@ int tpl_op_flags(tpl_op_t op) {
   if (!op) return -1;
   return (op->dist ? 1 : 0) | (op->eager ? 2 : 0) | (op->lay.val_i8 ? 4 : 0) |
          (op->lay.s_col16 ? 8 : 0) | (op->lay.b_col16 ? 16 : 0) | (op->last_one_graph ? 32 : 0) |
-         (!op->perm.empty() || op->part.local_order ? 64 : 0) | (op->pb_ld > 0 ? 128 : 0);
+         (!op->perm.empty() || op->part.local_order ? 64 : 0) | (op->pb_ld > 0 ? 128 : 0) |
+         (op->last_long_cache ? 256 : 0);
+}
+
+tpl_status tpl_op_set_long_cache(tpl_op_t op, int mode, uint64_t budget_bytes) {
+  return guarded([&] {
+    if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
+    if (mode < 0 || mode > 2) fail(TPL_ERR_INVALID_ARGUMENT, "long-row cache mode must be 0, 1 or 2");
+    set_device(op);
+    sync_checked(op);
+    // the buffer itself is resized by the next solve's ensure_state
+    op->long_cache = mode;
+    op->long_cache_budget = mode == 1 ? budget_bytes : 0;
+    drop_graphs(op);
+  });
+}
+uint64_t tpl_long_cache_default_budget(int64_t n) { return tpl::long_cache_default_budget(n); }
+uint64_t tpl_long_cache_rows(int mode, uint64_t budget_bytes, int64_t n, int64_t n_long,
+                             uint64_t kcap) {
+  return tpl::long_cache_rows(mode, budget_bytes, n, n_long, kcap);
 }
 
 tpl_status tpl_op_set_reorder(tpl_op_t op, int mode) {

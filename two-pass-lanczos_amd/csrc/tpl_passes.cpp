@@ -14,8 +14,8 @@ namespace tpl {
 
 namespace {
 enum GraphKind {
-  kGPass1 = 0,        // pass one: + the kP1* properties of the variant (kinds 0 .. 7)
-  kGPass2 = 8, kGPass2Steps,
+  kGPass1 = 0,        // pass one: + the kP1* properties of the variant (kinds 0 .. 15)
+  kGPass2 = 16, kGPass2Steps,
   kGTwoPassDev,       // one-graph solve: pass one, device f(T_k), pass two
   kGDevFtk,           // (timed variant) device f(T_k) + pass-two prologue
   kGPass2Dyn,         // (timed variant) the k - 1 step launches of a one-graph solve
@@ -24,11 +24,22 @@ enum GraphKind {
   kGPass2Batch,       // pass two of a batch group: one graph per (largest steps, NB)
   kGPass2BatchMulti,  // pass two of a batch-multi group whose columns took the same
                       // number of steps: one graph per (steps, NB, m)
+  kGLongCache = 64,   // + this: the sequence stores / reads the long-row cache (a solve of
+                      // tpl_lanczos_two_pass with the cache on; other kernels, other graphs)
 };
 // What tells one pass-one sequence (and its graph) from another, beside k: the basis is
 // stored (the standard pass), T_k's LU is eliminated as it goes (a device inv follows:
-// k_ftk_inv), kStampSteps steps carry start stamps (timed variant).
-enum P1Props { kP1Basis = 1, kP1Elim = 2, kP1Stamped = 4 };
+// k_ftk_inv), kStampSteps steps carry start stamps (timed variant), the long rows' sums
+// are stored in the long-row cache (tpl_lanczos_two_pass with the cache on).
+enum P1Props { kP1Basis = 1, kP1Elim = 2, kP1Stamped = 4, kP1Cache = 8 };
+
+// The long-row cache's row of step j (pass one stores it, pass two reads it), or nullptr:
+// the cache is not in use (long_cache_steps) or does not reach step j.
+inline double* cache_row(const tpl_op_s* op, int j) {
+  return (size_t)j <= long_cache_steps(op)
+             ? op->st.d_ycache + (size_t)(j - 1) * op->lay.lrows.size() : nullptr;
+}
+inline int graph_cache_kind(const tpl_op_s* op) { return long_cache_steps(op) ? kGLongCache : 0; }
 
 // r_j buffer of pass one: r_1 = b, then R[j % 3] (local view, and gather source).
 inline double* r_of(const tpl_op_s* op, int j) { return j == 1 ? op->b : op->R[j % 3]; }
@@ -89,9 +100,11 @@ void enqueue_p1_prologue(tpl_op_s* op) {
 // Pass one, step j (k = requested steps). elim: also eliminate row j - 3 of T_k's LU
 // (the one-graph inv, k_p1_axpy).
 // st1 / st2: start stamps of the step's k_p1_spmv / k_p1_axpy launch (live timing), or nullptr.
+// ycrow: the step's row of the long-row cache (one GPU: carried in the idle ypart), or nullptr.
 void enqueue_p1_step(tpl_op_s* op, int j, int k, double* Vcol, bool elim, unsigned long long* st1,
-                     unsigned long long* st2) {
-  const CsrDev A = csr_dev(op, true);
+                     unsigned long long* st2, double* ycrow) {
+  CsrDev A = csr_dev(op, true);
+  if (ycrow && !op->dist) A.ypart = ycrow;
   HIPCHK(launch::p1_spmv(A, op->st.S, rG_of(op, j), r_of(op, j), j >= 2 ? r_of(op, j - 1) : nullptr,
                          op->W, Vcol, j, op->stream, st1));
   if (op->dist) enqueue_p1_exchange_a(op, A);
@@ -118,7 +131,8 @@ static void enqueue_pass1(tpl_op_s* op, size_t k, int props, int reorth = 0) {
     const int i = j - js;  // stamp slots: spmv of step js + i at 2i, its axpy at 2i + 1
     unsigned long long* st1 = js && i >= 0 && i <= kStampSteps ? op->d_stamps + 2 * i : nullptr;
     unsigned long long* st2 = js && i >= 0 && i < kStampSteps ? op->d_stamps + 2 * i + 1 : nullptr;
-    enqueue_p1_step(op, j, (int)k, Vcol, (props & kP1Elim) != 0, st1, st2);
+    enqueue_p1_step(op, j, (int)k, Vcol, (props & kP1Elim) != 0, st1, st2,
+                    props & kP1Cache ? cache_row(op, j) : nullptr);
     if (reorth && j < (int)k) enqueue_reorth(op, j, reorth);
   }
 }
@@ -133,9 +147,16 @@ static void enqueue_pass2_init(tpl_op_s* op, size_t steps, double* Vout) {
 }
 
 // The pass-two step launch: step record j, the buffers at position t of their rotation
-// (a sweep: t = j; the profiler re-runs one step's record as the buffers turn).
+// (a sweep: t = j; the profiler re-runs one step's record as the buffers turn). The single
+// place that picks the kernel: k_p2_cached when the running tpl_lanczos_two_pass's pass one
+// stored step j's row of the long-row cache (cache_row), else the full k_p2_spmv.
 void launch_p2_step(tpl_op_s* op, const CsrDev& A, int j, int t, int nflush, double* Vcol) {
   const P2Rot v = p2_rot(op, t);
+  if (const double* yc = cache_row(op, j)) {
+    HIPCHK(launch::p2_cached(A, op->st.S, v.G, v.cur, j >= 2 ? v.prev : nullptr, v.next, op->x,
+                             Vcol, yc, op->st.d_ylrow, j, nflush, op->stream));
+    return;
+  }
   HIPCHK(launch::p2_spmv(A, op->st.S, v.G, v.cur, j >= 2 ? v.prev : nullptr, v.next, op->x, Vcol,
                          j, nflush, op->stream));
 }
@@ -232,19 +253,23 @@ static void run_graph(tpl_op_s* op, int kind, size_t key, Enq&& enqueue) {
 }
 
 static void run_pass1_graph(tpl_op_s* op, size_t k, int props) {
+  if (long_cache_steps(op)) props |= kP1Cache;
   run_graph(op, kGPass1 + props, k, [&] { enqueue_pass1(op, k, props); });
 }
 
 // Pass two without a basis. With live timing on, the prologue is launched on its own
 // and events bracket the graph of the steps - 1 step launches (tpl_op_pass_timing).
 void run_pass2(tpl_op_s* op, size_t steps) {
+  op->last_long_cache = steps >= 2 && long_cache_steps(op) > 0;
   if (!op->timing) {
-    run_graph(op, kGPass2, steps, [&] { enqueue_pass2(op, steps, nullptr); });
+    run_graph(op, kGPass2 + graph_cache_kind(op), steps,
+              [&] { enqueue_pass2(op, steps, nullptr); });
     return;
   }
   enqueue_pass2_init(op, steps, nullptr);
   HIPCHK(hipEventRecord(op->tev[2], op->stream));
-  run_graph(op, kGPass2Steps, steps, [&] { enqueue_pass2_steps(op, steps, nullptr); });
+  run_graph(op, kGPass2Steps + graph_cache_kind(op), steps,
+            [&] { enqueue_pass2_steps(op, steps, nullptr); });
   HIPCHK(hipEventRecord(op->tev[3], op->stream));
   op->p2_launches = (int64_t)steps - 1;
 }
@@ -275,6 +300,7 @@ void run_pass2_multi(tpl_op_s* op, size_t steps, size_t m) {
   if (op->dist) fail(TPL_ERR_UNSUPPORTED, "multi-function solve of a partitioned operator");
   if (m == 0 || m > op->xcols || steps > op->ycap || m > TPL_MULTI_MAX)
     fail(TPL_ERR_INVALID_ARGUMENT, "run_pass2_multi: buffers smaller than the request");
+  op->last_long_cache = false;
   run_graph(op, kGPass2Multi, steps * (TPL_MULTI_MAX + 1) + m,
             [&] { enqueue_pass2_multi(op, steps, m); });
 }
@@ -315,6 +341,7 @@ void run_pass1_batch(tpl_op_s* op, size_t k, int nb) {
 }
 void run_pass2_batch(tpl_op_s* op, size_t kmax, int nb) {
   check_batch(op, kmax, nb);
+  op->last_long_cache = false;
   run_graph(op, kGPass2Batch, kmax * 8 + (size_t)nb, [&] { enqueue_pass2_batch(op, kmax, nb); });
 }
 
@@ -356,6 +383,7 @@ void run_pass2_batch_multi(tpl_op_s* op, const size_t* steps, int nb, size_t m) 
   check_batch(op, kmax, nb);
   if (m == 0 || m > op->bat.mcols || m > TPL_MULTI_MAX)
     fail(TPL_ERR_INVALID_ARGUMENT, "batch-multi group: buffers smaller than the request");
+  op->last_long_cache = false;
   if (!even) {  // the launch list depends on every steps_c: not captured
     enqueue_pass2_batch_multi(op, steps, nb, m);
     return;
@@ -386,10 +414,12 @@ HostDecomp fetch_decomp(tpl_op_s* op) {
 void run_two_pass_dev(tpl_op_s* op, size_t k, int f) {
   const size_t key = 2 * k + (size_t)f;  // one graph per (k, f)
   const int elim = f == kDevInv ? kP1Elim : 0;  // T_k's LU eliminated during pass one
+  const int ck = graph_cache_kind(op);
+  op->last_long_cache = k >= 2 && ck != 0;
   if (!op->timing) {
     op->p1_samples = 0;  // the untimed graph records no launch stamps
-    run_graph(op, kGTwoPassDev, key, [&] {
-      enqueue_pass1(op, k, elim);
+    run_graph(op, kGTwoPassDev + ck, key, [&] {
+      enqueue_pass1(op, k, elim | (ck ? kP1Cache : 0));
       enqueue_ftk_dev(op, k, f);
       enqueue_pass2_dyn_steps(op, k);
       enqueue_pass2_tail(op);
@@ -407,7 +437,7 @@ void run_two_pass_dev(tpl_op_s* op, size_t k, int f) {
   HIPCHK(hipEventRecord(op->tev[1], op->stream));
   run_graph(op, kGDevFtk, key, [&] { enqueue_ftk_dev(op, k, f); });
   HIPCHK(hipEventRecord(op->tev[2], op->stream));
-  run_graph(op, kGPass2Dyn, k, [&] { enqueue_pass2_dyn_steps(op, k); });
+  run_graph(op, kGPass2Dyn + ck, k, [&] { enqueue_pass2_dyn_steps(op, k); });
   HIPCHK(hipEventRecord(op->tev[3], op->stream));
   enqueue_pass2_tail(op);
   op->p2_launches = (int64_t)k - 1;

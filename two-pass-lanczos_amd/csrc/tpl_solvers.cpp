@@ -145,6 +145,19 @@ void pass_two_one(tpl_op_s* op, const double* b, const double* alphas, size_t n_
   sync_checked(op);
 }
 
+// For the length of a tpl_lanczos_two_pass call: its pass one stores the long rows' sums in
+// the long-row cache and its pass two reads them (tpl_passes.cpp cache_row). No other entry
+// point opens one, so every other pass runs the full kernels and never reads a row another
+// solve wrote.
+struct LongCacheScope {
+  tpl_op_s* op;
+  explicit LongCacheScope(tpl_op_s* o) : op(o) {
+    op->use_long_cache = true;
+    op->last_long_cache = false;
+  }
+  ~LongCacheScope() { op->use_long_cache = false; }
+};
+
 // Where a k-step solve evaluates f(T_k): on the device for the built-in inv / exp of an
 // operator that is not partitioned, up to the mode's k (tpl_op_set_device_ftk).
 DevF device_f(const tpl_op_s* op, tpl_ftk_fn f, size_t k) {
@@ -295,6 +308,7 @@ tpl_status tpl_lanczos_two_pass(tpl_op_t op, const double* b, int64_t b_len, siz
     set_device(op);
     check_b(op, b, b_len);
     check_k(k);
+    const LongCacheScope cache(op);
     // the built-in inv / exp on the device: the whole solve one graph (pass one, f(T_k)
     // from the device alpha / beta, pass two), no host round trip between the passes
     const DevF dev_f = device_f(op, f, k);

@@ -276,6 +276,13 @@ class HipCsrOp:
         device, the whole solve one graph, 2 auto (default: device for k <= 128)."""
         check(_lib.tpl_op_set_device_ftk(self._op, int(mode)))
 
+    def set_long_cache(self, mode=2, budget_bytes=0):
+        """Long-row cache of lanczos_two_pass (tpl_op_set_long_cache): 0 / False off, 1 on
+        with at most budget_bytes of device memory, 2 auto (default: two vectors' bytes).
+        Pass one keeps the long rows' sums and pass two reads them back; the results are
+        bitwise the same either way. flags() bit 8 tells whether the last solve used it."""
+        check(_lib.tpl_op_set_long_cache(self._op, int(mode), int(budget_bytes)))
+
     def ftk_device(self, which: str, alphas, betas):
         """The device f(T_k) kernel alone ("inv" / "exp") on this operator's GPU:
         -> (y' = f(T_k) e_1, evaluated on the device?)."""
