@@ -112,8 +112,9 @@ int64_t tpl_op_nnz(tpl_op_t op);
  * tpl_op_permutation, reports it), bit 7: a replicated-long-row partition whose ranks
  * all-gather their norm partials and reduce them inside pass one's SpMV (no rank-total
  * launch), bit 8: the last pass two the operator ran read long rows' sums
- * from the long-row cache (tpl_op_set_long_cache: a tpl_lanczos_two_pass with the cache on;
- * any other entry point's pass two reads 0). -1 if op is NULL.                         */
+ * from the long-row cache (tpl_op_set_long_cache: a two-pass solve whose bit is in
+ * tpl_op_set_long_cache_solvers' mask — by default tpl_lanczos_two_pass alone — with the
+ * cache on; any other entry point's pass two reads 0). -1 if op is NULL.               */
 int tpl_op_flags(tpl_op_t op);
 /* Locality order (single-GPU operators; rebuilds the layout). mode 1: the device
  * holds P A P^T, the short rows sorted by the long rows (hub columns) they reference
@@ -338,11 +339,43 @@ tpl_status tpl_op_set_device_ftk(tpl_op_t op, int mode);
  * allocated with the solver state (a refused allocation leaves the operator as it was),
  * counted by tpl_op_device_bytes (rows x n_long x 8 bytes; plus 4 n_long for the long rows'
  * indices unless they are the operator's last rows, as the locality order puts them), and
- * not kept when the operator has no long rows. Only tpl_lanczos_two_pass uses it: the stand-alone
- * passes, the multi-function and batch solves and partitioned operators never do.
+ * not kept when the operator has no long rows. By default only tpl_lanczos_two_pass uses
+ * it; tpl_op_set_long_cache_solvers (below) adds the multi-function and batch two-pass
+ * solves. The stand-alone passes and partitioned operators never do.
  * Changing the mode or budget drops the cached graphs; the buffer is resized at the next
  * solve. tpl_op_flags bit 8 tells whether the last pass two read the cache.            */
 tpl_status tpl_op_set_long_cache(tpl_op_t op, int mode, uint64_t budget_bytes);
+/* Which two-pass solvers use the long-row cache while its mode is not 0: a mask of the bits
+ * below, default TPL_LONG_CACHE_TWO_PASS. A mask with any other bit is
+ * TPL_ERR_INVALID_ARGUMENT and leaves the operator unchanged. Results are bitwise the same
+ * whatever the mask.
+ *   A remainder column follows the bit of the entry point that was called (the single column
+ * after the groups of a batch call, the multi-function solve of a last column in a
+ * batch-multi call; a batch-multi call with m = 1 is a batch-multi call): one call is cached
+ * throughout or not at all. Partitioned operators, operators without long rows and the
+ * stand-alone passes (tpl_lanczos_pass_one[_batch], tpl_lanczos_pass_two[_multi | _batch |
+ * _batch_multi]) never cache, whatever the mask.
+ *   The multi-function solve uses the single solve's buffer. The batch solves keep a cache of
+ * the group's own beside the group's buffers while bit 4 or bit 8 is set: rows_b x n_long x
+ * NB doubles for groups of up to NB columns (plus the row-index table, as above), where
+ * rows_b = tpl_long_cache_rows(2, 0, n, n_long, kcap) in mode 2 (the budget is two group
+ * vectors' bytes, so a group caches as many steps as a single solve) and
+ * tpl_long_cache_rows(1, budget_bytes, n, n_long NB, kcap) in mode 1. It is counted by
+ * tpl_op_device_bytes, allocated by the next batch solve (a refused allocation leaves the
+ * operator as it was) and freed by the next batch solve after both bits are cleared.
+ * Changing the mask drops the cached graphs. tpl_op_flags bit 8 after a call with several
+ * groups tells of the last group's pass two, or the remainder's.
+ *   Measured at the 500k-arc headline, k = 500, every bit is faster in every
+ * run: batch s = 4 28.0 -> 24.9 ms (without bit 4 a batch call no longer beats s single
+ * solves), s = 2 14.8 -> 12.8, multi m = 4 9.33 -> 8.28, batch-multi s = 4, m = 4 32.7 ->
+ * 29.5. None met the project's condition for a recommendation by its letter (the protocol's
+ * single warm-up leaves one slow repetition that sets the spread; with two warm-ups all do),
+ * so none is recommended here.                                                           */
+#define TPL_LONG_CACHE_TWO_PASS 1u             /* tpl_lanczos_two_pass (default) */
+#define TPL_LONG_CACHE_TWO_PASS_MULTI 2u       /* tpl_lanczos_two_pass_multi */
+#define TPL_LONG_CACHE_TWO_PASS_BATCH 4u       /* tpl_lanczos_two_pass_batch */
+#define TPL_LONG_CACHE_TWO_PASS_BATCH_MULTI 8u /* tpl_lanczos_two_pass_batch_multi */
+tpl_status tpl_op_set_long_cache_solvers(tpl_op_t op, unsigned mask);
 /* Host arithmetic of the above: the default budget for n rows (2 x 8 x n padded to the
  * vector stride, a multiple of 64), and the steps cached under (mode, budget_bytes) for an
  * n-row operator with n_long long rows and a state capacity of kcap steps.              */

@@ -320,6 +320,11 @@ class HipCsrOp {
   void set_long_cache(int mode, uint64_t budget_bytes = 0) {
     detail::check(tpl_op_set_long_cache(op_, mode, budget_bytes));
   }
+  // The two-pass solvers that use it while it is on (tpl_op_set_long_cache_solvers): a mask
+  // of TPL_LONG_CACHE_*, default TPL_LONG_CACHE_TWO_PASS.
+  void set_long_cache_solvers(unsigned mask) {
+    detail::check(tpl_op_set_long_cache_solvers(op_, mask));
+  }
   tpl_op_t handle() const { return op_; }
 
  private:

@@ -65,15 +65,16 @@ def asm_path():
 
 # ------------------------------------------------------------------ reading it
 def mangled_fragment(kernel):
-    """'k_p1_spmv<58>' -> '9k_p1_spmvILi58EE', 'k_ftk_inv' -> '9k_ftk_invE' (Itanium)."""
-    m = re.fullmatch(r"(\w+)(?:<(-?\d+)>)?", kernel.strip())
+    """'k_p1_spmv<58>' -> '9k_p1_spmvILi58EE', 'k_bp2_cached<4, 3>' ->
+    '12k_bp2_cachedILi4ELi3EE', 'k_ftk_inv' -> '9k_ftk_invE' (Itanium)."""
+    m = re.fullmatch(r"(\w+)(?:<(-?\d+(?:\s*,\s*-?\d+)*)>)?", kernel.strip())
     if not m:
-        raise ValueError("kernel name %r: expected NAME or NAME<INT>" % kernel)
-    name, arg = m.group(1), m.group(2)
-    if arg is None:
+        raise ValueError("kernel name %r: expected NAME or NAME<INT[, INT ...]>" % kernel)
+    name, args = m.group(1), m.group(2)
+    if args is None:
         return "%d%sE" % (len(name), name)
-    lit = ("n" + arg[1:]) if arg.startswith("-") else arg
-    return "%d%sILi%sEE" % (len(name), name, lit)
+    lits = [("n" + a[1:]) if a.startswith("-") else a for a in re.split(r"\s*,\s*", args)]
+    return "%d%sI%sE" % (len(name), name, "".join("Li%sE" % l for l in lits))
 
 
 def find_symbol(text, kernel):

@@ -1,6 +1,7 @@
 // tpl_batch.h — the lock-step batch solve (tpl_lanczos_two_pass_batch): the per-column
 // device state of a group of NB columns and the launchers of the batch kernels
-// (tpl_k_batch_p1.hip, tpl_k_batch_p2.hip; device building blocks: tpl_kbatch.h).
+// (tpl_k_batch_p1.hip, tpl_k_batch_p2.hip, and tpl_k_batch_p2_cached.hip, whose launcher
+// tpl_launch.h declares; device building blocks: tpl_kbatch.h).
 // Plain data, shared by the kernels and the host units like tpl_device.h.
 //
 // A group's work vectors are INTERLEAVED: entry i of column c sits at v[i * NB + c], so a
@@ -49,8 +50,10 @@ hipError_t b_interleave(int nb, int64_t n, double* out, const double* B,
 hipError_t b_deinterleave(int nb, int64_t n, double* X, const double* in,
                           const int32_t* idx, hipStream_t s);
 hipError_t bp1_init(int nb, const CsrDev& A, const BatchDev& B, const double* b, hipStream_t s);
+// ycrow: the step's row of the group's long-row cache (the long rows' sums are stored
+// there, n_long x nb), or nullptr
 hipError_t bp1_spmv(int nb, const CsrDev& A, const BatchDev& B, const double* r_cur,
-                    const double* r_prev, double* W, int j, hipStream_t s);
+                    const double* r_prev, double* W, int j, double* ycrow, hipStream_t s);
 hipError_t bp1_axpy(int nb, const CsrDev& A, const BatchDev& B, const double* W,
                     const double* r_cur, double* r_next, int j, int k, hipStream_t s);
 hipError_t bp2_init(int nb, const CsrDev& A, const BatchDev& B, const double* b, double* v1,

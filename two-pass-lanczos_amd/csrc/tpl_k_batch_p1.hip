@@ -67,22 +67,35 @@ __global__ __launch_bounds__(kTPB) void k_bp1_init(CsrDev A, BatchDev B,
 // column from its norm partials (any count: the canonical partials() order, which is what
 // k_p1_spmv and k_p1_spmv_wide both compute), the breakdown test per column, the SpMV
 // gathering r_j * (1 / beta_{j-1}), w = y - beta_{j-1} v_{j-1}, the alpha partials.
+// ycrow: the step's row of the group's long-row cache (BatchBufs::d_ycache), where the long
+// rows' sums are kept for the same solve's pass two (k_bp2_cached), or nullptr.
 template <int NB, int FMT>
 __global__ __launch_bounds__(kTPB) void k_bp1_spmv(CsrDev A, BatchDev B,
                                                    const double* __restrict__ r_cur,
                                                    const double* __restrict__ r_prev,
-                                                   double* __restrict__ W, int j) {
+                                                   double* __restrict__ W, int j,
+                                                   double* __restrict__ ycrow) {
   __shared__ double red[4 * NB], redb[4 * NB];
   extern __shared__ double lds[];
   // the norm partials, the stop flags and beta_{j-2} ahead of the entries and gathers
   ColPartialRegs<NB, 1> pr;
   load_col_partials<NB, 1>(B.Pb, B.g2_ld, A.G2, pr);
-  int stop0[NB];
+  // beta_{j-2} of every column. NB = 2: loaded with the stop flags, ahead of the entries and
+  // gathers. NB = 4: held across those loads the 8 SGPRs are what tipped the instance into
+  // spilling SGPRs to VGPR lanes (up to 56 of them), so they are loaded at the start of the
+  // prologue instead, ahead of the reduction that hides them (measured not slower: DESIGN §6.1)
+  constexpr bool kLateNorms = NB > 2;
   double norm_prev[NB];
+  auto load_norms = [&] {
+#pragma unroll
+    for (int c = 0; c < NB; ++c)
+      norm_prev[c] = (j >= 2) ? B.norms[(size_t)c * (B.kcap + 1) + j - 2] : 1.0;
+  };
+  if constexpr (!kLateNorms) load_norms();
+  int stop0[NB];
 #pragma unroll
   for (int c = 0; c < NB; ++c) {
     stop0[c] = B.flags[8 * c];
-    norm_prev[c] = (j >= 2) ? B.norms[(size_t)c * (B.kcap + 1) + j - 2] : 1.0;
   }
   BEpiPass1<NB> epi;
   epi.r_cur = r_cur;
@@ -91,13 +104,15 @@ __global__ __launch_bounds__(kTPB) void k_bp1_spmv(CsrDev A, BatchDev B,
   epi.W = W;
   epi.Pa_long = B.Pa + A.n_chunks;
   epi.na_ld = B.na_ld;
+  epi.ycrow = ycrow;
 #pragma unroll
   for (int c = 0; c < NB; ++c) {
-    epi.alive[c] = false;
     epi.invN_cur[c] = epi.invN_prev[c] = epi.beta_sub[c] = 0.0;
   }
   epi.all_alive = false;
+  epi.alive = 0u;
   auto scale_fn = [&](double (&sc)[NB]) -> bool {
+    if constexpr (kLateNorms) load_norms();
     double sq[NB];
     finish_col_partials<NB, 1>(B.Pb, B.g2_ld, A.G2, pr, sq, redb);
     bool any = false;
@@ -121,13 +136,11 @@ __global__ __launch_bounds__(kTPB) void k_bp1_spmv(CsrDev A, BatchDev B,
       }
       epi.invN_cur[c] = 1.0 / beta;
       epi.beta_sub[c] = (j >= 2) ? beta : 0.0;
-      epi.alive[c] = true;
+      epi.alive |= 1u << c;
       sc[c] = epi.invN_cur[c];
       any = true;
     }
-    epi.all_alive = true;
-#pragma unroll
-    for (int c = 0; c < NB; ++c) epi.all_alive = epi.all_alive && epi.alive[c];
+    epi.all_alive = epi.alive == (1u << NB) - 1u;
     return any;
   };
   double acc[NB];
@@ -139,7 +152,7 @@ __global__ __launch_bounds__(kTPB) void k_bp1_spmv(CsrDev A, BatchDev B,
   if (threadIdx.x == 0)
 #pragma unroll
     for (int c = 0; c < NB; ++c)
-      if (epi.alive[c]) st_out(B.Pa + (size_t)c * B.na_ld + slot, acc[c]);
+      if (epi.is_alive(c)) st_out(B.Pa + (size_t)c * B.na_ld + slot, acc[c]);
 }
 
 // Pass one, step j (k_p1_axpy per column): alpha_j; r_{j+1} = w - alpha_j v_j; the
@@ -236,14 +249,14 @@ hipError_t bp1_init(int nb, const CsrDev& A, const BatchDev& B, const double* b,
   return hipGetLastError();
 }
 hipError_t bp1_spmv(int nb, const CsrDev& A, const BatchDev& B, const double* r_cur,
-                    const double* r_prev, double* W, int j, hipStream_t s) {
+                    const double* r_prev, double* W, int j, double* ycrow, hipStream_t s) {
   if (spmv_grid(A) <= 0) return hipGetLastError();
   TPL_NB_SWITCH(nb, return dispatch_fmt(
                         batch_fmt_of(A),
                         [&](auto F) {
                           hipLaunchKernelGGL((k_bp1_spmv<NB, decltype(F)::value>),
                                              dim3(spmv_grid(A)), dim3(kTPB), batch_lds_bytes(A), s,
-                                             A, B, r_cur, r_prev, W, j);
+                                             A, B, r_cur, r_prev, W, j, ycrow);
                         },
                         std::make_integer_sequence<int, kBFmtEnd>{}));
   return hipGetLastError();

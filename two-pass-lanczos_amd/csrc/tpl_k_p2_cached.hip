@@ -9,10 +9,12 @@
 // for every step the cache holds: no bins, no gathered lines, no LDS piece sums, no
 // hand-off — the short chunks as k_p2_spmv runs them, plus one thread per long row.
 //
-// Used by tpl_lanczos_two_pass alone (launch_p2_step, tpl_passes.cpp), for the pass two that
-// follows the pass one which filled the rows. Never by the stand-alone tpl_lanczos_pass_two
-// (with or without _multi), tpl_lanczos_two_pass_multi, the batch solves or a partitioned
-// operator: they run k_p2_spmv.
+// Used by the two-pass solvers in the operator's solver mask (tpl_op_set_long_cache_solvers:
+// tpl_lanczos_two_pass by default; tpl_lanczos_two_pass_multi, at nflush = 0, and the
+// remainder column of a batch solve on request) through launch_p2_step (tpl_passes.cpp), for
+// the pass two that follows the pass one which filled the rows. Never by the stand-alone
+// tpl_lanczos_pass_two (with or without _multi) or a partitioned operator: they run
+// k_p2_spmv. A batch group's sibling: k_bp2_cached (tpl_k_batch_p2_cached.hip).
 #include "tpl_klaunch.h"
 
 namespace tpl {

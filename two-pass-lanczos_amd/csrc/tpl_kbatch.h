@@ -160,14 +160,38 @@ struct BEpiPass1 {
   const double* r_cur;
   const double* r_prev;  // == r_cur (never used) at j == 1
   bool has_prev;
-  bool alive[NB];
+  // bit c: column c is alive at this step. One SGPR: as NB bools the columns' lane masks
+  // were 2 NB of the SGPRs k_bp1_spmv<4, FMT> spilled into VGPR lanes
+  unsigned alive;
   bool all_alive;
   double invN_cur[NB], invN_prev[NB], beta_sub[NB];
   double* W;
   double* Pa_long;  // column 0's long-row alpha partials (Pa + n_chunks)
   int na_ld;
+  double* ycrow;    // this step's row of the group's long-row cache (n_long x NB), or nullptr
+  __device__ __forceinline__ bool is_alive(int c) const { return (alive >> c) & 1u; }
+  // st_nb with the live columns as bits: 16-B stores when every column is alive, 8-B stores
+  // of the alive ones otherwise
+  __device__ __forceinline__ void store(double* __restrict__ p, int64_t i,
+                                        const double (&v)[NB]) const {
+    if (all_alive) {
+      double2* q = reinterpret_cast<double2*>(p + i * NB);
+#pragma unroll
+      for (int h = 0; h < NB / 2; ++h) q[h] = double2{v[2 * h], v[2 * h + 1]};
+    } else {
+#pragma unroll
+      for (int c = 0; c < NB; ++c)
+        if (is_alive(c)) p[i * NB + c] = v[c];
+    }
+  }
   __device__ __forceinline__ BPre1<NB> pre(int i) const {
     return BPre1<NB>{ld_nb<NB>(r_cur, i), ld_nb<NB>(r_prev, i)};
+  }
+  // Long row ri's finished sums, before its epilogue: kept for the pass two of the same
+  // solve (k_bp2_cached reads them back; EpiPass1::long_y per column). Stored as the group
+  // vectors are: the alive columns only, so a stopped column leaves the row's word as it was.
+  __device__ __forceinline__ void long_y(int ri, const double (&y)[NB]) const {
+    if (ycrow) store(ycrow, ri, y);
   }
   __device__ __forceinline__ void apply(int i, const double (&s)[NB], const BPre1<NB>& p,
                                         double (&acc)[NB]) const {
@@ -179,12 +203,12 @@ struct BEpiPass1 {
       w[c] = s[c] - beta_sub[c] * vp;
       acc[c] = fma(v, w[c], acc[c]);
     }
-    st_nb<NB>(W, i, w, alive, all_alive);
+    store(W, i, w);
   }
   __device__ __forceinline__ void long_alpha(int r, const double (&acc)[NB]) const {
 #pragma unroll
     for (int c = 0; c < NB; ++c)
-      if (alive[c]) st_out(Pa_long + (size_t)c * na_ld + r, acc[c]);
+      if (is_alive(c)) st_out(Pa_long + (size_t)c * na_ld + r, acc[c]);
   }
 };
 
@@ -242,6 +266,7 @@ struct BEpiPass2 {
     if (any_flush) st_nb<NB>(x, i, xn, flush, all_flush);
   }
   __device__ __forceinline__ void long_alpha(int, const double (&)[NB]) const {}
+  __device__ __forceinline__ void long_y(int, const double (&)[NB]) const {}
 };
 
 // ------------------------------------------------------ short rows (sliced ELL)
@@ -526,6 +551,7 @@ __device__ __forceinline__ void b_long_bin(const CsrDev& A, const BatchDev& B, i
   double acc[NB];
 #pragma unroll
   for (int col = 0; col < NB; ++col) acc[col] = 0.0;
+  epi.long_y(sg.ri, y);
   epi.apply(sg.row, y, pre, acc);
   epi.long_alpha(sg.ri, acc);
 }

@@ -6,6 +6,7 @@
 #include "tpl_device.h"
 
 namespace tpl {
+struct BatchDev;  // tpl_batch.h
 namespace launch {
 hipError_t spmv(const CsrDev& A, const double* x, double* y, hipStream_t s);
 hipError_t p1_init(const CsrDev& A, const DevState& S, const double* b, hipStream_t s);
@@ -35,6 +36,12 @@ hipError_t p2_cached(const CsrDev& A, const DevState& S, const double* xsrc, con
                      const double* v_prev, double* v_next, double* x, double* Vcol,
                      const double* ycache, const int32_t* lrow, int j, int nflush,
                      hipStream_t s);
+// the batch sibling (k_bp2_cached, tpl_k_batch_p2_cached.hip): step j of a group of nb
+// columns (the other batch launchers: tpl_batch.h) with the long rows' nb sums read from
+// `ycrow`, the step's row of the group's long-row cache (n_long x nb, a row's sums adjacent)
+hipError_t bp2_cached(int nb, const CsrDev& A, const BatchDev& B, const double* v_cur,
+                      const double* v_prev, double* v_next, double* x, const double* ycrow,
+                      const int32_t* lrow, int j, hipStream_t s);
 // pass-two step records (EpiPass2R) for steps 1 .. k-1; dyn: activity from the device count
 hipError_t p2_coefs(const DevState& S, int k, int dyn, hipStream_t s);
 hipError_t gemv_recon(int64_t n, int steps, const DevState& S, const double* V, double* x,

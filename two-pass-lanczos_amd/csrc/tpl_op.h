@@ -107,6 +107,15 @@ struct BatchBufs {
   size_t mcols = 0;
   double* d_mstage = nullptr;       // n x (nb mstage_cols), column-major: host X out
   size_t mstage_cols = 0;
+  // The group's long-row cache (tpl_op_set_long_cache_solvers bits 4 and 8): yrows x n_long
+  // x nb doubles, zeroed; a group of nb' columns keeps the sums of its pass-one step j at
+  // d_ycache + (j - 1) n_long nb', long row l's nb' sums adjacent. One allocation serves
+  // every group of a call: each group's pass one rewrites the rows before its pass two reads
+  // them. d_ylrow: the long rows' row indices behind the sums, or nullptr when they are the
+  // last rows (as SolverState's). nullptr: yrows == 0
+  double* d_ycache = nullptr;
+  size_t yrows = 0;
+  int32_t* d_ylrow = nullptr;
   BatchDev S{};
 };
 
@@ -187,11 +196,14 @@ struct tpl_op_s {
   // long-row cache: 0 off, 1 on within long_cache_budget bytes, 2 auto (the default budget)
   int long_cache = 2;
   uint64_t long_cache_budget = 0;
-  // set by tpl_lanczos_two_pass for the length of the call (LongCacheScope): its pass one
-  // stores the cache rows and its pass two reads them. Every other entry point leaves it
-  // false and runs today's kernels
+  // the solvers that use it when it is on (tpl_op_set_long_cache_solvers: TPL_LONG_CACHE_*)
+  unsigned long_cache_solvers = TPL_LONG_CACHE_TWO_PASS;
+  // set by a two-pass solver whose bit is in long_cache_solvers for the length of the call
+  // (LongCacheScope): its passes one store the cache rows and its passes two read them — a
+  // single column's in st, a batch group's in bat. Every other entry point leaves it false
+  // and runs the full kernels
   bool use_long_cache = false;
-  bool last_long_cache = false;     // the last tpl_lanczos_two_pass's pass two read the cache
+  bool last_long_cache = false;     // the last pass two the operator ran read the cache
   int64_t reorth_second = 0;        // second Gram-Schmidt passes of the last reorth solve
   // locality order (single GPU, tpl_op_set_reorder): the device works on P A P^T; vectors
   // cross the boundary through a gather (internal i <- caller's perm[i], back via iperm).
@@ -245,9 +257,13 @@ void ensure_state(tpl_op_s* op, size_t k, bool reorth = false);
 // n rows, n_long of them long, whose state holds kcap steps.
 uint64_t long_cache_default_budget(int64_t n);
 uint64_t long_cache_rows(int mode, uint64_t budget_bytes, int64_t n, int64_t n_long, uint64_t kcap);
-// Steps the operator's cache holds for the running tpl_lanczos_two_pass (0: not in use).
+// Steps the operator's cache holds for the running two-pass solve (0: not in use): of a
+// single column, and of a batch group.
 inline size_t long_cache_steps(const tpl_op_s* op) {
   return op->use_long_cache ? op->st.yrows : 0;
+}
+inline size_t batch_cache_steps(const tpl_op_s* op) {
+  return op->use_long_cache ? op->bat.yrows : 0;
 }
 void ensure_basis(tpl_op_s* op, size_t cols);
 // The m result vectors and the m x kcap coefficient table of a multi-function solve, for
@@ -257,7 +273,9 @@ void ensure_multi(tpl_op_s* op, size_t m);
 // The interleaved work vectors, per-column state and hand-off buffers of a batch group of
 // nb (2 or 4) columns and k steps, allocated on demand and counted in device_bytes. They
 // grow with nb and k; growing drops the cached graphs. A layout rebuild frees them
-// (free_batch): the next batch call allocates for the new layout.
+// (free_batch): the next batch call allocates for the new layout. The group's long-row
+// cache comes and goes with them, and is resized alone (built aside; the graphs dropped)
+// when only the cache's mode, budget or solver mask changed.
 void ensure_batch(tpl_op_s* op, int nb, size_t k);
 void free_batch(tpl_op_s* op);
 // The m result vectors and the coefficient table of a batch-multi group, for the batch
@@ -319,6 +337,7 @@ void enqueue_p1_step(tpl_op_s* op, int j, int k, double* Vcol, bool elim = false
                      unsigned long long* st1 = nullptr, unsigned long long* st2 = nullptr,
                      double* ycrow = nullptr);
 void launch_p2_step(tpl_op_s* op, const CsrDev& A, int j, int t, int nflush, double* Vcol);
+void launch_bp2_step(tpl_op_s* op, const CsrDev& A, int nb, int j);
 void enqueue_pass2(tpl_op_s* op, size_t steps, double* Vout);
 void enqueue_ftk_only(tpl_op_s* op, size_t k, int f, int scale);
 void run_pass_one(tpl_op_s* op, const double* b, size_t k, int mem, bool storeV, int reorth,

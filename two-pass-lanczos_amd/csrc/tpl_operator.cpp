@@ -394,8 +394,36 @@ void free_batch(tpl_op_s* op) {
   dev_free(op, b.d_vecs), dev_free(op, b.d_state), dev_free(op, b.d_P), dev_free(op, b.d_Pcnt);
   dev_free(op, b.d_stage);
   dev_free(op, b.d_mx), dev_free(op, b.d_my), dev_free(op, b.d_mstage);
+  dev_free(op, b.d_ycache);
   b = BatchBufs{};
 }
+namespace {
+// Steps a batch group's long-row cache should hold for buffers of w columns and kc steps:
+// none unless a batch solver is in the mask. Mode 2: a group caches as many steps as a
+// single solve (the budget is two GROUP vectors' bytes); mode 1: budget_bytes over the
+// w n_long doubles of a step.
+size_t wanted_batch_cache_rows(const tpl_op_s* op, int w, size_t kc) {
+  const unsigned batch_bits = TPL_LONG_CACHE_TWO_PASS_BATCH | TPL_LONG_CACHE_TWO_PASS_BATCH_MULTI;
+  if (op->dist || !(op->long_cache_solvers & batch_bits) || w <= 0) return 0;
+  const int64_t nl = (int64_t)op->lay.lrows.size();
+  return (size_t)long_cache_rows(op->long_cache, op->long_cache_budget, op->part.n,
+                                 op->long_cache == 1 ? nl * w : nl, kc);
+}
+// A zeroed cache of `rows` steps for groups of up to w columns (alloc_cache's layout: the row
+// indices behind the sums unless the long rows are the last rows).
+void alloc_batch_cache(tpl_op_s* op, double** ycache, int32_t** ylrow, int w, size_t rows) {
+  if (rows == 0) return;
+  const std::vector<int32_t>& lr = op->lay.lrows;
+  const size_t sums = rows * lr.size() * (size_t)w * sizeof(double);
+  const size_t table = op->lay.s_identity ? 0 : (lr.size() * sizeof(int32_t) + 7) / 8 * 8;
+  dev_alloc(op, ycache, sums + table);
+  HIPCHK(hipMemset(*ycache, 0, sums));
+  if (table) {
+    *ylrow = reinterpret_cast<int32_t*>(*ycache + rows * lr.size() * (size_t)w);
+    HIPCHK(hipMemcpy(*ylrow, lr.data(), lr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+}
+} // namespace
 // Freed before they grow, as the basis is; sized for the batch buffers' nb and kcap.
 void ensure_batch_multi(tpl_op_s* op, size_t m, bool stage) {
   BatchBufs& b = op->bat;
@@ -432,7 +460,27 @@ void ensure_batch_multi(tpl_op_s* op, size_t m, bool stage) {
 // [p2c 8 nb kc] [Pa nb NA] [Pb nb G2].
 void ensure_batch(tpl_op_s* op, int nb, size_t k) {
   BatchBufs& b = op->bat;
-  if (nb <= b.nb && k <= b.kcap) return;
+  if (nb <= b.nb && k <= b.kcap) {
+    // the buffers do; the group's long-row cache alone when its mode, budget or solver
+    // mask changed since they were sized: built aside, so a refused allocation leaves the
+    // operator as it was
+    const size_t rows = wanted_batch_cache_rows(op, b.nb, b.kcap);
+    if (rows == b.yrows) return;
+    double* yc = nullptr;
+    int32_t* yl = nullptr;
+    try {
+      alloc_batch_cache(op, &yc, &yl, b.nb, rows);
+    } catch (...) {
+      dev_free(op, yc);
+      throw;
+    }
+    std::swap(b.d_ycache, yc);
+    b.d_ylrow = yl;
+    b.yrows = rows;
+    dev_free(op, yc);
+    drop_graphs(op);
+    return;
+  }
   const int w = std::max(nb, b.nb);
   const size_t kc = std::max<size_t>(std::max(k, b.kcap), 16);
   drop_graphs(op);
@@ -473,6 +521,9 @@ void ensure_batch(tpl_op_s* op, int nb, size_t k) {
     S.kcap = (int32_t)kc;
     S.na_ld = (int32_t)na;
     S.g2_ld = (int32_t)g2;
+    const size_t rows = wanted_batch_cache_rows(op, w, kc);
+    alloc_batch_cache(op, &b.d_ycache, &b.d_ylrow, w, rows);
+    b.yrows = rows;
   } catch (...) {
     free_batch(op);
     throw;
@@ -762,6 +813,22 @@ tpl_status tpl_op_set_long_cache(tpl_op_t op, int mode, uint64_t budget_bytes) {
     op->long_cache = mode;
     op->long_cache_budget = mode == 1 ? budget_bytes : 0;
     drop_graphs(op);
+  });
+}
+tpl_status tpl_op_set_long_cache_solvers(tpl_op_t op, unsigned mask) {
+  return guarded([&] {
+    if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
+    const unsigned all = TPL_LONG_CACHE_TWO_PASS | TPL_LONG_CACHE_TWO_PASS_MULTI |
+                         TPL_LONG_CACHE_TWO_PASS_BATCH | TPL_LONG_CACHE_TWO_PASS_BATCH_MULTI;
+    if (mask & ~all)
+      fail(TPL_ERR_INVALID_ARGUMENT, "long-row cache solver mask has bits above TPL_LONG_CACHE_*");
+    if (!op->plan_only) {  // a host-only plan keeps the mask and has nothing to drop
+      set_device(op);
+      sync_checked(op);
+      // the group's buffer is resized or freed by the next batch solve's ensure_batch
+      drop_graphs(op);
+    }
+    op->long_cache_solvers = mask;
   });
 }
 uint64_t tpl_long_cache_default_budget(int64_t n) { return tpl::long_cache_default_budget(n); }

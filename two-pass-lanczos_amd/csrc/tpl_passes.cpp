@@ -24,8 +24,8 @@ enum GraphKind {
   kGPass2Batch,       // pass two of a batch group: one graph per (largest steps, NB)
   kGPass2BatchMulti,  // pass two of a batch-multi group whose columns took the same
                       // number of steps: one graph per (steps, NB, m)
-  kGLongCache = 64,   // + this: the sequence stores / reads the long-row cache (a solve of
-                      // tpl_lanczos_two_pass with the cache on; other kernels, other graphs)
+  kGLongCache = 64,   // + this: the sequence stores / reads the long-row cache (a two-pass
+                      // solve with the cache on for it; other kernels, other graphs)
 };
 // What tells one pass-one sequence (and its graph) from another, beside k: the basis is
 // stored (the standard pass), T_k's LU is eliminated as it goes (a device inv follows:
@@ -40,6 +40,14 @@ inline double* cache_row(const tpl_op_s* op, int j) {
              ? op->st.d_ycache + (size_t)(j - 1) * op->lay.lrows.size() : nullptr;
 }
 inline int graph_cache_kind(const tpl_op_s* op) { return long_cache_steps(op) ? kGLongCache : 0; }
+// The same for a batch group of nb columns: the row of step j in the group's own cache.
+inline double* batch_cache_row(const tpl_op_s* op, int j, int nb) {
+  return (size_t)j <= batch_cache_steps(op)
+             ? op->bat.d_ycache + (size_t)(j - 1) * op->lay.lrows.size() * (size_t)nb : nullptr;
+}
+inline int batch_graph_cache_kind(const tpl_op_s* op) {
+  return batch_cache_steps(op) ? kGLongCache : 0;
+}
 
 // r_j buffer of pass one: r_1 = b, then R[j % 3] (local view, and gather source).
 inline double* r_of(const tpl_op_s* op, int j) { return j == 1 ? op->b : op->R[j % 3]; }
@@ -300,8 +308,8 @@ void run_pass2_multi(tpl_op_s* op, size_t steps, size_t m) {
   if (op->dist) fail(TPL_ERR_UNSUPPORTED, "multi-function solve of a partitioned operator");
   if (m == 0 || m > op->xcols || steps > op->ycap || m > TPL_MULTI_MAX)
     fail(TPL_ERR_INVALID_ARGUMENT, "run_pass2_multi: buffers smaller than the request");
-  op->last_long_cache = false;
-  run_graph(op, kGPass2Multi, steps * (TPL_MULTI_MAX + 1) + m,
+  op->last_long_cache = steps >= 2 && long_cache_steps(op) > 0;
+  run_graph(op, kGPass2Multi + graph_cache_kind(op), steps * (TPL_MULTI_MAX + 1) + m,
             [&] { enqueue_pass2_multi(op, steps, m); });
 }
 
@@ -316,9 +324,22 @@ static void enqueue_pass1_batch(tpl_op_s* op, size_t k, int nb) {
   auto r_of = [&](int j) { return j == 1 ? bb.b : bb.R[j % 3]; };
   for (int j = 1; j <= (int)k; ++j) {
     HIPCHK(launch::bp1_spmv(nb, A, S, r_of(j), j >= 2 ? r_of(j - 1) : nullptr, bb.W, j,
-                            op->stream));
+                            batch_cache_row(op, j, nb), op->stream));
     HIPCHK(launch::bp1_axpy(nb, A, S, bb.W, r_of(j), bb.R[(j + 1) % 3], j, (int)k, op->stream));
   }
+}
+// The batch pass-two step launch: step j of a group of nb columns over the ring (v_j in
+// R[j % 3]). The single place that picks the batch step kernel: k_bp2_cached when the
+// running batch solve's pass one, for this group, stored step j's row of the group's
+// long-row cache (batch_cache_row), else the full k_bp2_spmv.
+void launch_bp2_step(tpl_op_s* op, const CsrDev& A, int nb, int j) {
+  BatchBufs& bb = op->bat;
+  double *vp = j >= 2 ? bb.R[(j + 2) % 3] : nullptr, *vc = bb.R[j % 3], *vn = bb.R[(j + 1) % 3];
+  if (const double* yc = batch_cache_row(op, j, nb)) {
+    HIPCHK(launch::bp2_cached(nb, A, bb.S, vc, vp, vn, bb.x, yc, bb.d_ylrow, j, op->stream));
+    return;
+  }
+  HIPCHK(launch::bp2_spmv(nb, A, bb.S, vc, vp, vn, bb.x, j, op->stream));
 }
 static void enqueue_pass2_batch(tpl_op_s* op, size_t kmax, int nb) {
   const CsrDev A = csr_dev(op);
@@ -326,9 +347,7 @@ static void enqueue_pass2_batch(tpl_op_s* op, size_t kmax, int nb) {
   const BatchDev& S = bb.S;
   HIPCHK(launch::bp2_init(nb, A, S, bb.b, bb.R[1], bb.x, op->stream));
   HIPCHK(launch::bp2_coefs(nb, S, (int)kmax, op->stream));
-  for (int j = 1; j < (int)kmax; ++j)
-    HIPCHK(launch::bp2_spmv(nb, A, S, bb.R[j % 3], j >= 2 ? bb.R[(j + 2) % 3] : nullptr,
-                            bb.R[(j + 1) % 3], bb.x, j, op->stream));
+  for (int j = 1; j < (int)kmax; ++j) launch_bp2_step(op, A, nb, j);
 }
 static void check_batch(const tpl_op_s* op, size_t k, int nb) {
   if (op->dist) fail(TPL_ERR_UNSUPPORTED, "batch solve of a partitioned operator");
@@ -337,12 +356,14 @@ static void check_batch(const tpl_op_s* op, size_t k, int nb) {
 }
 void run_pass1_batch(tpl_op_s* op, size_t k, int nb) {
   check_batch(op, k, nb);
-  run_graph(op, kGPass1Batch, k * 8 + (size_t)nb, [&] { enqueue_pass1_batch(op, k, nb); });
+  run_graph(op, kGPass1Batch + batch_graph_cache_kind(op), k * 8 + (size_t)nb,
+            [&] { enqueue_pass1_batch(op, k, nb); });
 }
 void run_pass2_batch(tpl_op_s* op, size_t kmax, int nb) {
   check_batch(op, kmax, nb);
-  op->last_long_cache = false;
-  run_graph(op, kGPass2Batch, kmax * 8 + (size_t)nb, [&] { enqueue_pass2_batch(op, kmax, nb); });
+  op->last_long_cache = kmax >= 2 && batch_cache_steps(op) > 0;
+  run_graph(op, kGPass2Batch + batch_graph_cache_kind(op), kmax * 8 + (size_t)nb,
+            [&] { enqueue_pass2_batch(op, kmax, nb); });
 }
 
 // ---- m functions of every column of a group (tpl_lanczos_two_pass_batch_multi): the
@@ -362,7 +383,7 @@ static void enqueue_pass2_batch_multi(tpl_op_s* op, const size_t* steps, int nb,
   HIPCHK(launch::bp2_coefs0(nb, S, (int)kmax, op->stream));
   for (int j = 1; j < (int)kmax; ++j) {
     double *vp = bb.R[(j + 2) % 3], *vc = bb.R[j % 3], *vn = bb.R[(j + 1) % 3];
-    HIPCHK(launch::bp2_spmv(nb, A, S, vc, j >= 2 ? vp : nullptr, vn, bb.x, j, op->stream));
+    launch_bp2_step(op, A, nb, j);
     bool any = false;
     for (int c = 0; c < nb; ++c)
       any = any || (j < (int)steps[c] && p2_flush(j, (int)steps[c] - 1) > 0);
@@ -383,12 +404,13 @@ void run_pass2_batch_multi(tpl_op_s* op, const size_t* steps, int nb, size_t m) 
   check_batch(op, kmax, nb);
   if (m == 0 || m > op->bat.mcols || m > TPL_MULTI_MAX)
     fail(TPL_ERR_INVALID_ARGUMENT, "batch-multi group: buffers smaller than the request");
-  op->last_long_cache = false;
+  op->last_long_cache = kmax >= 2 && batch_cache_steps(op) > 0;
   if (!even) {  // the launch list depends on every steps_c: not captured
     enqueue_pass2_batch_multi(op, steps, nb, m);
     return;
   }
-  run_graph(op, kGPass2BatchMulti, (kmax * 8 + (size_t)nb) * (TPL_MULTI_MAX + 1) + m,
+  run_graph(op, kGPass2BatchMulti + batch_graph_cache_kind(op),
+            (kmax * 8 + (size_t)nb) * (TPL_MULTI_MAX + 1) + m,
             [&] { enqueue_pass2_batch_multi(op, steps, nb, m); });
 }
 

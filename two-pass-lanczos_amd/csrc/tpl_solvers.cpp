@@ -145,14 +145,16 @@ void pass_two_one(tpl_op_s* op, const double* b, const double* alphas, size_t n_
   sync_checked(op);
 }
 
-// For the length of a tpl_lanczos_two_pass call: its pass one stores the long rows' sums in
-// the long-row cache and its pass two reads them (tpl_passes.cpp cache_row). No other entry
-// point opens one, so every other pass runs the full kernels and never reads a row another
-// solve wrote.
+// For the length of a two-pass solve whose bit (TPL_LONG_CACHE_*) is in the operator's
+// solver mask: every pass one of the call stores the long rows' sums in the long-row cache
+// and the pass two that follows it reads them (tpl_passes.cpp cache_row, batch_cache_row) —
+// a batch call's groups in the group's cache, its remainder column in the single solve's,
+// so one call is cached throughout or not at all. Only the four two-pass solvers open one,
+// so every other pass runs the full kernels and never reads a row another solve wrote.
 struct LongCacheScope {
   tpl_op_s* op;
-  explicit LongCacheScope(tpl_op_s* o) : op(o) {
-    op->use_long_cache = true;
+  LongCacheScope(tpl_op_s* o, unsigned bit) : op(o) {
+    op->use_long_cache = (op->long_cache_solvers & bit) != 0;
     op->last_long_cache = false;
   }
   ~LongCacheScope() { op->use_long_cache = false; }
@@ -308,7 +310,7 @@ tpl_status tpl_lanczos_two_pass(tpl_op_t op, const double* b, int64_t b_len, siz
     set_device(op);
     check_b(op, b, b_len);
     check_k(k);
-    const LongCacheScope cache(op);
+    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS);
     // the built-in inv / exp on the device: the whole solve one graph (pass one, f(T_k)
     // from the device alpha / beta, pass two), no host round trip between the passes
     const DevF dev_f = device_f(op, f, k);
@@ -473,6 +475,7 @@ tpl_status tpl_lanczos_two_pass_multi(tpl_op_t op, const double* b, int64_t b_le
     check_b(op, b, b_len);
     check_k(k);
     const TimingOff untimed(op);
+    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS_MULTI);
     two_pass_multi(op, b, k, fs, f_users, m, x_out, mem);
   });
 }
@@ -688,6 +691,7 @@ tpl_status tpl_lanczos_two_pass_batch(tpl_op_t op, const double* B, int64_t b_le
     check_b(op, B, b_len);
     check_k(k);
     const TimingOff untimed(op);
+    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS_BATCH);
     two_pass_batch(op, B, s, k, f, f_user, x_out, mem);
   });
 }
@@ -822,6 +826,7 @@ tpl_status tpl_lanczos_two_pass_batch_multi(tpl_op_t op, const double* B, int64_
     check_b(op, B, b_len);
     check_k(k);
     const TimingOff untimed(op);
+    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS_BATCH_MULTI);
     if (m == 1) {  // one function: the batch solve
       two_pass_batch(op, B, s, k, fs[0], f_users ? f_users[0] : nullptr, x_out, mem);
       return;

@@ -13,6 +13,8 @@ from . import _lib
 from . import algorithms, error, ftk, solvers
 from .error import DataLoaderError, LanczosError, LanczosErrorKind, TplError
 from .operator import HipCsrOp, HostPlan, device_count, locality_order, refresh_uploaded
+from .operator import (LONG_CACHE_TWO_PASS, LONG_CACHE_TWO_PASS_BATCH,
+                       LONG_CACHE_TWO_PASS_BATCH_MULTI, LONG_CACHE_TWO_PASS_MULTI)
 from .solvers import (lanczos, lanczos_multi, lanczos_two_pass, lanczos_two_pass_batch,
                       lanczos_two_pass_batch_multi, lanczos_two_pass_multi)
 
@@ -23,4 +25,6 @@ __all__ = [
     "lanczos", "lanczos_two_pass", "lanczos_multi", "lanczos_two_pass_multi", "lanczos_two_pass_batch", "lanczos_two_pass_batch_multi", "algorithms", "solvers", "error", "ftk", "HipCsrOp",
     "LanczosError", "LanczosErrorKind", "TplError", "DataLoaderError", "device_count",
     "locality_order", "HostPlan", "refresh_uploaded",
+    "LONG_CACHE_TWO_PASS", "LONG_CACHE_TWO_PASS_MULTI", "LONG_CACHE_TWO_PASS_BATCH",
+    "LONG_CACHE_TWO_PASS_BATCH_MULTI",
 ]

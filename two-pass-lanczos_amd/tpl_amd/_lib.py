@@ -147,6 +147,7 @@ tpl_op_step_samples = _sig("tpl_op_step_samples", c_int, c_void_p, PD, PD, POINT
 tpl_op_set_device_ftk = _sig("tpl_op_set_device_ftk", c_int, c_void_p, c_int)
 tpl_op_device_bytes = _sig("tpl_op_device_bytes", c_int, c_void_p, POINTER(ctypes.c_uint64))
 tpl_op_set_long_cache = _sig("tpl_op_set_long_cache", c_int, c_void_p, c_int, ctypes.c_uint64)
+tpl_op_set_long_cache_solvers = _sig("tpl_op_set_long_cache_solvers", c_int, c_void_p, ctypes.c_uint)
 tpl_long_cache_default_budget = _sig("tpl_long_cache_default_budget", ctypes.c_uint64, c_int64)
 tpl_long_cache_rows = _sig("tpl_long_cache_rows", ctypes.c_uint64, c_int, ctypes.c_uint64, c_int64,
                            c_int64, ctypes.c_uint64)
@@ -257,3 +258,4 @@ EXPORTED += ["tpl_dist_op_create_replicated", "tpl_op_local_rows", "tpl_dist_par
              "tpl_dist_op_create_halo", "tpl_dist_choose_partition", "tpl_dist_op_create_auto",
              "tpl_operand_key"]
 EXPORTED += ["tpl_op_set_long_cache", "tpl_long_cache_default_budget", "tpl_long_cache_rows"]
+EXPORTED += ["tpl_op_set_long_cache_solvers"]

@@ -17,6 +17,12 @@ import numpy as np
 from . import _lib
 from .error import TplError, check
 
+# tpl.h TPL_LONG_CACHE_*: the solvers HipCsrOp.set_long_cache_solvers names
+LONG_CACHE_TWO_PASS = 1
+LONG_CACHE_TWO_PASS_MULTI = 2
+LONG_CACHE_TWO_PASS_BATCH = 4
+LONG_CACHE_TWO_PASS_BATCH_MULTI = 8
+
 _ctx_lock = threading.Lock()
 _contexts: dict[int, int] = {}
 
@@ -283,6 +289,14 @@ class HipCsrOp:
         bitwise the same either way. flags() bit 8 tells whether the last solve used it."""
         check(_lib.tpl_op_set_long_cache(self._op, int(mode), int(budget_bytes)))
 
+    def set_long_cache_solvers(self, mask=LONG_CACHE_TWO_PASS):
+        """Which two-pass solvers use the long-row cache while it is on
+        (tpl_op_set_long_cache_solvers): a mask of LONG_CACHE_TWO_PASS (the default),
+        LONG_CACHE_TWO_PASS_MULTI, LONG_CACHE_TWO_PASS_BATCH and
+        LONG_CACHE_TWO_PASS_BATCH_MULTI. A remainder column follows the bit of the solver that
+        was called. Results are bitwise the same whatever the mask."""
+        check(_lib.tpl_op_set_long_cache_solvers(self._op, int(mask)))
+
     def ftk_device(self, which: str, alphas, betas):
         """The device f(T_k) kernel alone ("inv" / "exp") on this operator's GPU:
         -> (y' = f(T_k) e_1, evaluated on the device?)."""
@@ -334,6 +348,7 @@ class HipCsrOp:
 
 HostPlan.schedule = HipCsrOp.schedule
 HostPlan.kernel_variant = HipCsrOp.kernel_variant
+HostPlan.set_long_cache_solvers = HipCsrOp.set_long_cache_solvers  # a plan keeps the mask
 
 
 # -- the caller's own matrix as `operator` (the reference's call sites pass `&a.as_ref()`,
