@@ -192,6 +192,13 @@ int tpl_ftk_exp(const double* alphas, size_t n_alphas, const double* betas, size
 int tpl_ftk_sq(const double* alphas, size_t n_alphas, const double* betas, size_t n_betas,
                double* y_out, size_t y_cap, size_t* y_len, char* err_msg, size_t err_cap,
                void* user);
+/* exp_t: y' = exp(t T_k) e_1 — exp(tA) b at time t. `user` points to one double, t; NULL:
+ * non-zero return with a message. tpl_ftk_exp on the arrays t * alphas, t * betas (every
+ * entry times t, rounded once), so bitwise what a caller gets who scales T_k and calls
+ * tpl_ftk_exp.                                                                  */
+int tpl_ftk_exp_t(const double* alphas, size_t n_alphas, const double* betas, size_t n_betas,
+                  double* y_out, size_t y_cap, size_t* y_len, char* err_msg, size_t err_cap,
+                  void* user);
 
 /* ---- high-level API: src/solvers.rs ------------------------------------- */
 /* solvers::lanczos (src/solvers.rs:46-107): standard pass (V_k kept in HBM),
@@ -231,6 +238,26 @@ tpl_status tpl_lanczos_two_pass_multi(tpl_op_t op, const double* b, int64_t b_le
 tpl_status tpl_lanczos_multi(tpl_op_t op, const double* b, int64_t b_len, size_t k,
                              const tpl_ftk_fn* fs, void** f_users, size_t m,
                              double* x_out, int mem);
+/* exp(t_i A) b for the m times ts[0..m) — the action of the matrix exponential at a list of
+ * times — over one Krylov space: column i of x_out (column-major n x m, leading dimension
+ * n) is ||b|| V_k exp(t_i T_k) e_1. One pass one; then, unless the operator's device-f mode
+ * is 0 (tpl_op_set_device_ftk) or k > 1800, every exp(t_i T_k) e_1 at once on the device,
+ * one workgroup per time (k_ftk_exp_times: tpl_lanczos_two_pass's device exp on the
+ * tridiagonal t_i * alphas, t_i * betas, with its accuracy and its hand-back rules), with no
+ * host work between the passes but one synchronisation; a time the device hands back, and
+ * in mode 0 or past k = 1800 every time, is evaluated on the host by tpl_ftk_exp_t, in
+ * index order; then ONE pass two for all m results. on_device (m entries, or NULL):
+ * 1 where the device's y was used. Column i is bitwise tpl_lanczos_pass_two on pass one's
+ * decomposition with the y that was used; in mode 0 the whole result is bitwise
+ * tpl_lanczos_two_pass_multi's with fs[i] = tpl_ftk_exp_t, f_users[i] = &ts[i]. Errors: those
+ * of tpl_lanczos_two_pass_multi (a host failure is reported for its index); m == 0,
+ * m > TPL_MULTI_MAX, NULL ts or x_out, a non-finite t_i: TPL_ERR_INVALID_ARGUMENT, before any
+ * device work; a partitioned operator: TPL_ERR_UNSUPPORTED. tpl_op_flags bit 5 reads 0
+ * afterwards (the call is not one graph); the long-row cache follows the
+ * TPL_LONG_CACHE_TWO_PASS_MULTI bit; no live timing.                                  */
+tpl_status tpl_lanczos_two_pass_exp_times(tpl_op_t op, const double* b, int64_t b_len, size_t k,
+                                          const double* ts, size_t m, double* x_out, int mem,
+                                          int32_t* on_device);
 /* ---- f(A) b_1 ... f(A) b_s in one lock-step run (an extension: the reference's
  *      solvers::lanczos_two_pass takes one b) -----------------------------------------
  * The other axis: one f, s right-hand sides. Every b_c has its own Krylov space, its own
@@ -387,6 +414,14 @@ uint64_t tpl_long_cache_rows(int mode, uint64_t budget_bytes, int64_t n, int64_t
  * *on_device = 0 when the exp kernel handed the case back to the host (y_out then 0).  */
 tpl_status tpl_op_ftk_device(tpl_op_t op, int which, const double* alphas, size_t n,
                              const double* betas, double* y_out, int* on_device);
+/* The same for k_ftk_exp_times alone: exp(t_i T_k) e_1 for the m times ts[0..m) (1 <= m <=
+ * TPL_MULTI_MAX, 1 <= n <= 1800) into y_out (host, column-major n x m, leading dimension
+ * n, unscaled); on_device[i] = 0 where the kernel handed time i back (that column then 0).
+ * Column i and on_device[i] are bitwise tpl_op_ftk_device(op, 1, ...) on t_i * alphas,
+ * t_i * betas.                                                                       */
+tpl_status tpl_op_ftk_exp_times_device(tpl_op_t op, const double* alphas, size_t n,
+                                       const double* betas, const double* ts, size_t m,
+                                       double* y_out, int32_t* on_device);
 
 /* ---- low-level API: src/algorithms/ -------------------------------------- */
 /* Per-step callback of lanczos_standard (LanczosCallback, src/algorithms/mod.rs:82-86):

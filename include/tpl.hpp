@@ -4,6 +4,7 @@
  *
  *   tpl::solvers::lanczos / lanczos_two_pass          src/solvers.rs:46-107, 133-175
  *   tpl::solvers::lanczos_two_pass_multi / lanczos_multi   (none: m functions, one Krylov run)
+ *   tpl::solvers::lanczos_two_pass_exp_times               (none: exp(t_i A) b at m times)
  *   tpl::algorithms::lanczos_standard                 src/algorithms/lanczos.rs:55-156
  *   tpl::algorithms::lanczos_pass_one                 src/algorithms/lanczos_two_pass.rs:65-110
  *   tpl::algorithms::lanczos_pass_two[_with_basis]    src/algorithms/lanczos_two_pass.rs:128-166
@@ -495,6 +496,21 @@ inline Mat lanczos_multi(const HipCsrOp& op, const std::vector<double>& b, size_
                                 void** u, size_t m, double* x) {
                                return tpl_lanczos_multi(o, bp, n, kk, fn, u, m, x, TPL_MEM_HOST);
                              });
+}
+// exp(t_i A) b for the times ts by one two-pass run (tpl_lanczos_two_pass_exp_times): pass one
+// once, every exp(t_i T_k) e_1 at once on the device (a time the device hands back runs the
+// host tpl_ftk_exp_t), one pass two. Column i of the n x m result is exp(ts[i] A) b;
+// on_device, if given, is resized to m: 1 where the device's y was used.
+inline Mat lanczos_two_pass_exp_times(const HipCsrOp& op, const std::vector<double>& b, size_t k,
+                                      const std::vector<double>& ts,
+                                      std::vector<int32_t>* on_device = nullptr) {
+  detail::check_b(op, b);
+  Mat x(op.nrows(), ts.size());
+  if (on_device) on_device->assign(ts.size(), 0);
+  detail::check(tpl_lanczos_two_pass_exp_times(op.handle(), b.data(), (int64_t)b.size(), k,
+                                               ts.data(), ts.size(), x.data.data(), TPL_MEM_HOST,
+                                               on_device ? on_device->data() : nullptr));
+  return x;
 }
 // One lock-step two-pass run for the s columns of B (n x s): pass one for all columns
 // together, f(T_k) e_1 per column on the host in column order, one pass two. Column c of the

@@ -125,6 +125,15 @@ extern "C" {
     fn tpl_lanczos_two_pass_multi(op: *mut TplOp, b: *const f64, b_len: i64, k: usize,
                                   fs: *const FtkFn, f_users: *mut *mut c_void, m: usize,
                                   x_out: *mut f64, mem: c_int) -> c_int;
+    fn tpl_lanczos_two_pass_exp_times(op: *mut TplOp, b: *const f64, b_len: i64, k: usize,
+                                      ts: *const f64, m: usize, x_out: *mut f64, mem: c_int,
+                                      on_device: *mut i32) -> c_int;
+    fn tpl_op_ftk_exp_times_device(op: *mut TplOp, alphas: *const f64, n: usize,
+                                   betas: *const f64, ts: *const f64, m: usize,
+                                   y_out: *mut f64, on_device: *mut i32) -> c_int;
+    fn tpl_ftk_exp_t(alphas: *const f64, n_alphas: usize, betas: *const f64, n_betas: usize,
+                     y_out: *mut f64, y_cap: usize, y_len: *mut usize, err_msg: *mut c_char,
+                     err_cap: usize, user: *mut c_void) -> c_int;
     fn tpl_lanczos_multi(op: *mut TplOp, b: *const f64, b_len: i64, k: usize,
                          fs: *const FtkFn, f_users: *mut *mut c_void, m: usize,
                          x_out: *mut f64, mem: c_int) -> c_int;
@@ -803,6 +812,33 @@ where
 {
     let _ = stack;
     solve_multi(operator, b, k, f_tk_solvers, tpl_lanczos_two_pass_multi)
+}
+
+/// exp(t_i A) b for the times `ts` by ONE two-pass run (no reference counterpart): pass one
+/// once, every exp(t_i T_k) e_1 at once on the device (a time the device hands back runs the
+/// native host `tpl_ftk_exp_t`), one pass two. Returns the n x m result and, per time, whether
+/// the device's y was used.
+pub fn lanczos_two_pass_exp_times<O: HipOperand>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    k: usize,
+    ts: &[f64],
+    stack: &mut MemStack,
+) -> Result<(Mat<f64>, Vec<bool>), LanczosError> {
+    let _ = stack;
+    let bv = column(b);
+    let m = ts.len();
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n * m];
+        let mut on = vec![0i32; m];
+        let _g = op.lock.lock().unwrap();
+        unsafe {
+            check(tpl_lanczos_two_pass_exp_times(op.op, bv.as_ptr(), bv.len() as i64, k,
+                                                 ts.as_ptr(), m, x.as_mut_ptr(), TPL_MEM_HOST,
+                                                 on.as_mut_ptr()))?;
+        }
+        Ok((column_major(&x, op.n, m), on.iter().map(|&v| v != 0).collect()))
+    })?
 }
 
 /// The one-pass sibling of `lanczos_two_pass_multi`: one standard pass, one reconstruction

@@ -8,6 +8,7 @@
 //        -> here: implicit-shift QL on the tridiagonal T_k; Q is applied through its
 //        recorded rotations (O(k^2)) instead of being accumulated (O(k^3)).
 //   sq : y' = T_k^2 e_1 (tests/correctness.rs:287-299).
+//   exp_t: exp on t T_k, t from `user` (no reference counterpart: exp(tA) b at a time t).
 // inv and sq are O(k), exp O(k^2) host work on at most 2k doubles: small next to
 // the 2k-1 device SpMVs of a solve.
 #include <cmath>
@@ -205,6 +206,24 @@ int tpl_ftk_exp(const double* alphas, size_t n_alphas, const double* betas, size
     y_out[R.i + 1] = -R.s * a + R.c * b;
   }
   return 0;
+}
+
+int tpl_ftk_exp_t(const double* alphas, size_t n_alphas, const double* betas, size_t n_betas,
+                  double* y_out, size_t y_cap, size_t* y_len, char* err_msg, size_t err_cap,
+                  void* user) {
+  if (!user) {
+    if (y_len) *y_len = n_alphas;
+    put_err(err_msg, err_cap, "exp_t: `user` must point to the time t");
+    return 1;
+  }
+  // t T_k: every entry times t, rounded once (what numpy's t * alphas gives, and what the
+  // device's k_ftk_exp_times forms); the sizes are tpl_ftk_exp's to check
+  const double t = *static_cast<const double*>(user);
+  std::vector<double> ta(n_alphas), tb(n_betas);
+  for (size_t i = 0; i < n_alphas; ++i) ta[i] = t * alphas[i];
+  for (size_t i = 0; i < n_betas; ++i) tb[i] = t * betas[i];
+  return tpl_ftk_exp(ta.data(), n_alphas, tb.data(), n_betas, y_out, y_cap, y_len, err_msg, err_cap,
+                     nullptr);
 }
 
 } // extern "C"

@@ -23,6 +23,11 @@ hipError_t permute(int64_t n, int cols, double* out, int64_t ldo, const double* 
                    const int32_t* idx, hipStream_t s);
 hipError_t ftk_inv(const DevState& S, int kcap, int scale, hipStream_t s);
 hipError_t ftk_exp(const DevState& S, int kcap, int scale, hipStream_t s);
+// exp(t_i T_k) e_1 for the m times ts[0..m), one workgroup each (k_ftk_exp_times,
+// tpl_k_ftk_exp_times.hip): column i of Y (columns ldy >= kcap apart) and back[i] = 0, or a
+// zero column and back[i] = 1 where k_ftk_exp would hand the case back
+hipError_t ftk_exp_times(const DevState& S, int kcap, const double* ts, int m, double* Y, int ldy,
+                         int32_t* back, int scale, hipStream_t s);
 hipError_t p2_init(int64_t n, const DevState& S, const double* b, double* v1, double* x,
                    double* Vcol, int dyn, hipStream_t s);
 // nflush: x terms the step applies (tpl::p2_flush: every third step and the last)

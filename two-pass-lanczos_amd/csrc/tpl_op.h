@@ -184,6 +184,11 @@ struct tpl_op_s {
   // apart) and the coefficient table Y (xcols columns, ycap apart); nullptr: xcols == 0
   double *d_X = nullptr, *d_Y = nullptr;
   size_t xcols = 0, ycap = 0;
+  // exp(t_i A) b at m times (ensure_exp_times): the times (TPL_MULTI_MAX doubles), the
+  // kernel's hand-back entries (TPL_MULTI_MAX int32) and their pinned host mirror; nullptr
+  // until the first tpl_lanczos_two_pass_exp_times / tpl_op_ftk_exp_times_device call
+  double* d_exp_ts = nullptr;
+  int32_t *d_exp_back = nullptr, *h_exp_back = nullptr;
   tpl::BatchBufs bat;               // lock-step batch solves (ensure_batch)
   std::map<std::pair<int, size_t>, tpl::GraphExec> graphs;
   // device allocations of this operator (pointer -> bytes): tpl_op_device_bytes
@@ -270,6 +275,10 @@ void ensure_basis(tpl_op_s* op, size_t cols);
 // the state's current kcap (ensure_state first). They grow with m and kcap; growing drops
 // the cached graphs.
 void ensure_multi(tpl_op_s* op, size_t m);
+// The two small buffers of the exp-times calls (op->d_exp_ts, op->d_exp_back) and the pinned
+// mirror of the second: allocated on the first such call, counted in device_bytes, freed
+// with the operator. No graph holds them.
+void ensure_exp_times(tpl_op_s* op);
 // The interleaved work vectors, per-column state and hand-off buffers of a batch group of
 // nb (2 or 4) columns and k steps, allocated on demand and counted in device_bytes. They
 // grow with nb and k; growing drops the cached graphs. A layout rebuild frees them

@@ -14,6 +14,7 @@ tpl_op_s::~tpl_op_s() {
   graphs.clear();
   for (const auto& kv : allocs) hipFree(const_cast<void*>(kv.first));  // every dev_alloc
   if (st.h_state) hipHostFree(st.h_state);
+  if (h_exp_back) hipHostFree(h_exp_back);
   if (ev0) hipEventDestroy(ev0);
   if (ev1) hipEventDestroy(ev1);
   for (hipEvent_t e : tev)
@@ -388,6 +389,19 @@ void ensure_multi(tpl_op_s* op, size_t m) {
   dev_alloc(op, &op->d_Y, cols * cap * sizeof(double));
   op->xcols = cols;
   op->ycap = cap;
+}
+void ensure_exp_times(tpl_op_s* op) {
+  if (!op->d_exp_ts) {
+    dev_alloc(op, &op->d_exp_ts, TPL_MULTI_MAX * sizeof(double));
+    HIPCHK(hipMemset(op->d_exp_ts, 0, TPL_MULTI_MAX * sizeof(double)));
+  }
+  if (!op->d_exp_back) {
+    dev_alloc(op, &op->d_exp_back, TPL_MULTI_MAX * sizeof(int32_t));
+    HIPCHK(hipMemset(op->d_exp_back, 0, TPL_MULTI_MAX * sizeof(int32_t)));
+  }
+  if (!op->h_exp_back)
+    HIPCHK(hipHostMalloc((void**)&op->h_exp_back, TPL_MULTI_MAX * sizeof(int32_t),
+                         hipHostMallocDefault));
 }
 void free_batch(tpl_op_s* op) {
   BatchBufs& b = op->bat;

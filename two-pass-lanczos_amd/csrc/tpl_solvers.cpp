@@ -1,6 +1,8 @@
 // tpl_solvers.cpp — the solver entry points of the C ABI (include/tpl.h): the SpMV, the
 // passes on their own, and the one- and two-pass solves with their f(T_k) on the host or
 // on the device.
+#include <cmath>
+
 #include "tpl_op.h"
 
 using namespace tpl;
@@ -524,6 +526,64 @@ tpl_status tpl_lanczos_pass_two_multi(tpl_op_t op, const double* b, int64_t b_le
   });
 }
 
+tpl_status tpl_lanczos_two_pass_exp_times(tpl_op_t op, const double* b, int64_t b_len, size_t k,
+                                          const double* ts, size_t m, double* x_out, int mem,
+                                          int32_t* on_device) {
+  return guarded([&] {
+    check_multi(op, ts && x_out, m);
+    check_b(op, b, b_len);
+    check_k(k);
+    for (size_t i = 0; i < m; ++i)
+      if (!std::isfinite(ts[i])) fail(TPL_ERR_INVALID_ARGUMENT, "every time t_i must be finite");
+    const TimingOff untimed(op);
+    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS_MULTI);
+    op->last_one_graph = false;
+    if (on_device) std::fill(on_device, on_device + m, 0);
+    ensure_state(op, k);
+    ensure_multi(op, m);
+    ensure_exp_times(op);
+    // 1. pass one, once; 2. straight behind it on the stream every exp(t_i T_k) e_1 at once
+    //    (steps_taken stays on the device), y_i = y'_i * ||b|| into the coefficient table
+    const bool dev = op->device_ftk != 0 && k <= kDevExpMaxK;
+    if (dev)
+      HIPCHK(hipMemcpyAsync(op->d_exp_ts, ts, m * sizeof(double), hipMemcpyHostToDevice,
+                            op->stream));
+    run_pass_one(op, b, k, mem, false, false);
+    if (dev) {
+      HIPCHK(launch::ftk_exp_times(op->st.S, (int)k, op->d_exp_ts, (int)m, op->d_Y, (int)op->ycap,
+                                   op->d_exp_back, 1, op->stream));
+      HIPCHK(hipMemcpyAsync(op->h_exp_back, op->d_exp_back, m * sizeof(int32_t),
+                            hipMemcpyDeviceToHost, op->stream));
+    }
+    const HostDecomp d = fetch_decomp(op);  // the call's one synchronisation before pass two
+    if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+    if (d.steps == 0) {
+      zero_out_cols(op, x_out, m, mem);
+      return;
+    }
+    // 3. the times handed back (without the device: all of them) on the host, in index
+    //    order; only their columns are uploaded
+    std::vector<double> Y, y;
+    double t = 0.0;
+    for (size_t i = 0; i < m; ++i) {
+      if (dev && !op->h_exp_back[i]) continue;
+      if (Y.empty()) Y.resize(m * d.steps);
+      t = ts[i];
+      call_ftk(&tpl_ftk_exp_t, &t, d, y);
+      double* col = Y.data() + i * d.steps;
+      for (size_t j = 0; j < d.steps; ++j) col[j] = y[j] * d.b_norm;
+      HIPCHK(hipMemcpyAsync(op->d_Y + i * op->ycap, col, d.steps * sizeof(double),
+                            hipMemcpyHostToDevice, op->stream));
+    }
+    // 4. one pass two for all of them
+    run_pass2_multi(op, d.steps, m);
+    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+    sync_checked(op);
+    if (on_device)
+      for (size_t i = 0; i < m; ++i) on_device[i] = dev && !op->h_exp_back[i] ? 1 : 0;
+  });
+}
+
 tpl_status tpl_op_reorth_second_passes(tpl_op_t op, int64_t* count) {
   return guarded([&] {
     if (!op || !count) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -566,6 +626,45 @@ tpl_status tpl_op_ftk_device(tpl_op_t op, int which, const double* alphas, size_
     HIPCHK(hipMemcpyAsync(flags, S.flags, kFlagBytes, hipMemcpyDeviceToHost, op->stream));
     sync_checked(op);
     *on_device = flags[4] ? 0 : 1;
+  });
+}
+
+tpl_status tpl_op_ftk_exp_times_device(tpl_op_t op, const double* alphas, size_t n,
+                                       const double* betas, const double* ts, size_t m,
+                                       double* y_out, int32_t* on_device) {
+  return guarded([&] {
+    if (!op || !alphas || !ts || !y_out || !on_device || (n > 1 && !betas))
+      fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (m == 0 || m > (size_t)TPL_MULTI_MAX)
+      fail(TPL_ERR_INVALID_ARGUMENT, "m must be between 1 and TPL_MULTI_MAX");
+    if (n == 0) fail(TPL_ERR_INVALID_ARGUMENT, "n must be >= 1");
+    if (n > kDevExpMaxK) fail(TPL_ERR_UNSUPPORTED, "k above the device f(T_k) bound");
+    set_device(op);
+    if (op->dist) fail(TPL_ERR_UNSUPPORTED, "multi-function solve of a partitioned operator");
+    ensure_state(op, n);
+    ensure_multi(op, m);
+    ensure_exp_times(op);
+    // the solver state as pass one leaves it: steps_taken = n, ||b|| = 1, no error
+    const int32_t flags[kFlagBytes / 4] = {0, 0, (int32_t)n, 0, 0, 0, 0, 0};
+    const double one = 1.0;
+    const DevState& S = op->st.S;
+    HIPCHK(hipMemcpyAsync(S.flags, flags, kFlagBytes, hipMemcpyHostToDevice, op->stream));
+    HIPCHK(hipMemcpyAsync(S.norms, &one, sizeof(double), hipMemcpyHostToDevice, op->stream));
+    HIPCHK(hipMemcpyAsync(S.alphas, alphas, n * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    if (n > 1)
+      HIPCHK(hipMemcpyAsync(S.betas, betas, (n - 1) * sizeof(double), hipMemcpyHostToDevice,
+                            op->stream));
+    HIPCHK(hipMemcpyAsync(op->d_exp_ts, ts, m * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    HIPCHK(launch::ftk_exp_times(S, (int)n, op->d_exp_ts, (int)m, op->d_Y, (int)op->ycap,
+                                 op->d_exp_back, 0, op->stream));
+    HIPCHK(hipMemcpy2DAsync(y_out, n * sizeof(double), op->d_Y, op->ycap * sizeof(double),
+                            n * sizeof(double), m, hipMemcpyDeviceToHost, op->stream));
+    HIPCHK(hipMemcpyAsync(op->h_exp_back, op->d_exp_back, m * sizeof(int32_t),
+                          hipMemcpyDeviceToHost, op->stream));
+    sync_checked(op);
+    for (size_t i = 0; i < m; ++i) on_device[i] = op->h_exp_back[i] ? 0 : 1;
   });
 }
 

@@ -107,6 +107,9 @@ TPL_MULTI_MAX = 64
 tpl_lanczos_two_pass_multi = _sig("tpl_lanczos_two_pass_multi", c_int, c_void_p, c_void_p, c_int64,
                                   c_size_t, POINTER(c_void_p), POINTER(c_void_p), c_size_t,
                                   c_void_p, c_int)
+tpl_lanczos_two_pass_exp_times = _sig("tpl_lanczos_two_pass_exp_times", c_int, c_void_p, c_void_p,
+                                      c_int64, c_size_t, PD, c_size_t, c_void_p, c_int,
+                                      POINTER(c_int32))
 tpl_lanczos_multi = _sig("tpl_lanczos_multi", c_int, c_void_p, c_void_p, c_int64, c_size_t,
                          POINTER(c_void_p), POINTER(c_void_p), c_size_t, c_void_p, c_int)
 tpl_lanczos_pass_two_multi = _sig("tpl_lanczos_pass_two_multi", c_int, c_void_p, c_void_p, c_int64,
@@ -161,6 +164,8 @@ tpl_locality_order = _sig("tpl_locality_order", c_int, c_int64, POINTER(c_int64)
 tpl_op_reorth_second_passes = _sig("tpl_op_reorth_second_passes", c_int, c_void_p, POINTER(c_int64))
 tpl_op_ftk_device = _sig("tpl_op_ftk_device", c_int, c_void_p, c_int, PD, c_size_t, PD, PD,
                          POINTER(c_int))
+tpl_op_ftk_exp_times_device = _sig("tpl_op_ftk_exp_times_device", c_int, c_void_p, PD, c_size_t,
+                                   PD, PD, c_size_t, PD, POINTER(c_int32))
 tpl_op_set_order_groups = _sig("tpl_op_set_order_groups", c_int, c_void_p, c_int32)
 tpl_op_order_groups = _sig("tpl_op_order_groups", c_int32, c_void_p)
 
@@ -185,6 +190,10 @@ tpl_ftk_exp = _sig("tpl_ftk_exp", c_int, PD, c_size_t, PD, c_size_t, PD, c_size_
                    POINTER(c_size_t), POINTER(c_char), c_size_t, c_void_p)
 tpl_ftk_sq = _sig("tpl_ftk_sq", c_int, PD, c_size_t, PD, c_size_t, PD, c_size_t,
                   POINTER(c_size_t), POINTER(c_char), c_size_t, c_void_p)
+# exp(t T_k) e_1: `user` points to one double, the time t
+FTK_EXP_T_PTR = ctypes.cast(lib.tpl_ftk_exp_t, c_void_p).value
+tpl_ftk_exp_t = _sig("tpl_ftk_exp_t", c_int, PD, c_size_t, PD, c_size_t, PD, c_size_t,
+                     POINTER(c_size_t), POINTER(c_char), c_size_t, c_void_p)
 
 # Every symbol include/tpl.h declares (checked by tests/test_boundary.py).
 EXPORTED = [
@@ -259,3 +268,4 @@ EXPORTED += ["tpl_dist_op_create_replicated", "tpl_op_local_rows", "tpl_dist_par
              "tpl_operand_key"]
 EXPORTED += ["tpl_op_set_long_cache", "tpl_long_cache_default_budget", "tpl_long_cache_rows"]
 EXPORTED += ["tpl_op_set_long_cache_solvers"]
+EXPORTED += ["tpl_ftk_exp_t", "tpl_lanczos_two_pass_exp_times", "tpl_op_ftk_exp_times_device"]

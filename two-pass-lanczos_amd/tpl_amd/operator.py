@@ -310,6 +310,22 @@ class HipCsrOp:
                                      y.ctypes.data_as(POINTER(c_double)), byref(on)))
         return y, bool(on.value)
 
+    def ftk_exp_times_device(self, alphas, betas, ts):
+        """The device kernel of ``lanczos_two_pass_exp_times`` alone: exp(t_i T_k) e_1 for every
+        time of ``ts`` -> (Y of shape (n, m), strides (1, n), unscaled; (m,) bool array: evaluated
+        on the device? — a handed-back column is zero)."""
+        a = np.ascontiguousarray(alphas, dtype=np.float64)
+        b = np.ascontiguousarray(betas, dtype=np.float64)
+        t = np.ascontiguousarray(np.atleast_1d(np.asarray(ts, dtype=np.float64)).reshape(-1))
+        n, m = a.shape[0], t.shape[0]
+        y = np.zeros((max(m, 1), n))
+        on = np.zeros(max(m, 1), dtype=np.int32)
+        check(_lib.tpl_op_ftk_exp_times_device(
+            self._op, a.ctypes.data_as(POINTER(c_double)), n, b.ctypes.data_as(POINTER(c_double)),
+            t.ctypes.data_as(POINTER(c_double)), m, y.ctypes.data_as(POINTER(c_double)),
+            on.ctypes.data_as(POINTER(ctypes.c_int32))))
+        return y[:m].T, on[:m].astype(bool)
+
     def enable_timing(self, on: bool = True):
         """Record HIP events inside the captured passes of later solves."""
         check(_lib.tpl_op_enable_timing(self._op, 1 if on else 0))

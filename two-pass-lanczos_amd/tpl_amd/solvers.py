@@ -25,10 +25,17 @@ f(A) b_1 ... f(A) b_s for the columns of ``B`` in one lock-step two-pass run. It
 both axes: f_i(A) b_c for m functions and the s columns of ``B`` in one run. It returns shape
 (n, m, s) with strides (1, n, n m) — ``X[:, i, c]`` is bitwise the single solve of ``B[:, c]``
 with ``f_tk_solvers[i]`` evaluated on the host.
+
+``lanczos_two_pass_exp_times(operator, b, k, ts)`` (no reference counterpart) is the action of
+the matrix exponential at a list of times: exp(t_i A) b for every t_i over one Krylov space,
+every exp(t_i T_k) e_1 evaluated at once on the device between the two shared passes. It
+returns shape (n, m) with strides (1, n).
 """
 from __future__ import annotations
 
 import ctypes
+
+import numpy as np
 
 from . import _lib, ftk
 from ._vec import Cols, Vec
@@ -89,6 +96,25 @@ def lanczos_two_pass_multi(operator, b, k: int, f_tk_solvers):
     """f_i(A) b, i = 0 .. m-1, by ONE two-pass run: pass one once, every f_i(T_k) on the
     host, one pass two that regenerates the basis once for all m results."""
     return _run_multi(_lib.tpl_lanczos_two_pass_multi, operator, b, k, f_tk_solvers)
+
+
+def lanczos_two_pass_exp_times(operator, b, k: int, ts, return_on_device: bool = False):
+    """exp(t_i A) b for the m times ``ts`` by ONE two-pass run: pass one once, every
+    exp(t_i T_k) e_1 at once on the device (one workgroup per time; a time the device hands
+    back, and with ``set_device_ftk(0)`` every time, runs the native host ``exp_t``), one pass
+    two for all m results. Column i is ``lanczos_two_pass`` with ``ftk.exp_t(ts[i])`` to the
+    device exp's accuracy. With ``return_on_device`` also the (m,) bool array of the times
+    whose y the device computed."""
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(ts, dtype=np.float64)).reshape(-1))
+    m = int(t.shape[0])
+    operator = as_operator(operator)
+    bv = Vec(b)
+    x = bv.empty(max(m, 1), operator.nrows())  # C-order (m, n) == column-major (n, m)
+    on = np.zeros(max(m, 1), dtype=np.int32)
+    check(_lib.tpl_lanczos_two_pass_exp_times(
+        operator.handle, bv.ptr, bv.n, k, t.ctypes.data_as(_lib.PD), m, Vec.ptr_of(x), bv.mem,
+        on.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return (x.T, on.astype(bool)) if return_on_device else x.T
 
 
 def lanczos_two_pass_batch(operator, B, k: int, f_tk_solver):
