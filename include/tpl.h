@@ -54,7 +54,10 @@ enum { TPL_MEM_HOST = 0, TPL_MEM_DEVICE = 1 };
 typedef struct tpl_ctx_s* tpl_ctx_t; /* one GPU + one HIP stream          */
 typedef struct tpl_op_s* tpl_op_t;   /* device-resident CSR operator A    */
 
-/* Thread-local message of the last failing call ("" after success). */
+/* Thread-local message of the last failing call ("" after success). A successful
+ * tpl_op_destroy / tpl_ctx_destroy / tpl_dist_destroy leaves it, and tpl_last_error_detail's
+ * record, as they were: a binding's finalizer may run between a failed call and the
+ * caller's read of its error.                                                          */
 const char* tpl_last_error(void);
 /* The fields of the last failing call's LanczosErrorKind (src/error.rs:20-58), so a
  * binding rebuilds the variant itself instead of parsing the message:
@@ -114,7 +117,9 @@ int64_t tpl_op_nnz(tpl_op_t op);
  * launch), bit 8: the last pass two the operator ran read long rows' sums
  * from the long-row cache (tpl_op_set_long_cache: a two-pass solve whose bit is in
  * tpl_op_set_long_cache_solvers' mask — by default tpl_lanczos_two_pass alone — with the
- * cache on; any other entry point's pass two reads 0). -1 if op is NULL.               */
+ * cache on; any other entry point's pass two reads 0), bit 9: that pass two ran fused — two
+ * launches for all its steps (tpl_op_set_fused_pass_two; bit 8 is set as well).
+ * -1 if op is NULL.                                                                    */
 int tpl_op_flags(tpl_op_t op);
 /* Locality order (single-GPU operators; rebuilds the layout). mode 1: the device
  * holds P A P^T, the short rows sorted by the long rows (hub columns) they reference
@@ -403,6 +408,32 @@ tpl_status tpl_op_set_long_cache(tpl_op_t op, int mode, uint64_t budget_bytes);
 #define TPL_LONG_CACHE_TWO_PASS_BATCH 4u       /* tpl_lanczos_two_pass_batch */
 #define TPL_LONG_CACHE_TWO_PASS_BATCH_MULTI 8u /* tpl_lanczos_two_pass_batch_multi */
 tpl_status tpl_op_set_long_cache_solvers(tpl_op_t op, unsigned mask);
+/* The fused pass two of tpl_lanczos_two_pass (single-GPU operators). With the
+ * long-row cache holding every step's sums, a long row's whole pass-two history follows from
+ * its own cache column, and so does that of a closed short row (every column a long row or
+ * the row itself) once the long rows' v_j are known; the open short rows and the long rows
+ * they reference (the hub set H) step together in one workgroup. Pass two is then two
+ * launches (k_p2_hub, k_p2_rows) instead of steps - 1 step launches, bitwise the same x.
+ *   mode 0: off; 2 (default): whenever all of these hold — the long rows are the operator's
+ *   last rows (the locality order puts them there), 1 to 2048 of them, no short row wider
+ *   than 4 entries, |H| <= 256 with every column of an open row in H, the call is
+ *   tpl_lanczos_two_pass without re-orthogonalisation on a single GPU, and the long-row
+ *   cache is on for it and holds every step the call asked for (rows >= k).
+ * Otherwise, and in every other entry point, the step launches run as before. The path
+ * allocates nothing: its small tables (the open rows' entries, H's rows) come with the
+ * layout in every mode, and the cache rows hold the long rows' v_j after the solve (the next
+ * solve's pass one rewrites them). With live timing on, pass2_spmv_us of tpl_op_pass_timing
+ * stays the bracketed time over pass2_launches = steps - 1: on this path the pass-two time
+ * per regenerated step, not per launch. Changing the mode drops the cached graphs.
+ * tpl_op_flags bit 9 tells whether the last pass two ran fused.                          */
+tpl_status tpl_op_set_fused_pass_two(tpl_op_t op, int mode);
+/* The layout's verdict without a GPU, for a CSR matrix (columns ascending per row) and a
+ * short-row threshold as tpl_op_set_schedule takes it (<= 0: auto): *eligible = 1 when the
+ * row classes allow the fused pass two (the placement of the long rows is the operator's
+ * matter), *n_open = the open short rows, *n_hub = |H| (n_open itself when more than 256
+ * rows are open). Returns 0, or -1 for NULL / negative arguments.                       */
+int tpl_fused_pass_two_rows(int64_t n, const int64_t* row_ptr, const int32_t* col_idx,
+                            int short_row_max, int* eligible, int64_t* n_open, int64_t* n_hub);
 /* Host arithmetic of the above: the default budget for n rows (2 x 8 x n padded to the
  * vector stride, a multiple of 64), and the steps cached under (mode, budget_bytes) for an
  * n-row operator with n_long long rows and a state capacity of kcap steps.              */

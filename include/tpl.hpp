@@ -321,6 +321,9 @@ class HipCsrOp {
   void set_long_cache(int mode, uint64_t budget_bytes = 0) {
     detail::check(tpl_op_set_long_cache(op_, mode, budget_bytes));
   }
+  // The fused pass two of lanczos_two_pass (tpl_op_set_fused_pass_two): 0 off, 2 auto (the
+  // default); flags() bit 9 tells whether the last pass two ran fused.
+  void set_fused_pass_two(int mode) { detail::check(tpl_op_set_fused_pass_two(op_, mode)); }
   // The two-pass solvers that use it while it is on (tpl_op_set_long_cache_solvers): a mask
   // of TPL_LONG_CACHE_*, default TPL_LONG_CACHE_TWO_PASS.
   void set_long_cache_solvers(unsigned mask) {

@@ -104,6 +104,12 @@ constexpr int kLongEpiRows = kTPB;  // one replicated long row per thread (k_lon
 constexpr int kPbRanks = 8;          // most ranks whose norm partials k_p1_spmv reduces itself
 constexpr int kWinMax = 2048;        // short-chunk column window in LDS: at most this many columns
 constexpr int kWinLoads = kWinMax / 256;  // window loads per thread
+// The fused pass two (tpl_k_p2_fused.hip, tpl_layout.h FusedP2): widest short row, most rows
+// of the hub set (one thread each), most long rows (their v_j are staged in LDS twice over:
+// 32 KiB).
+constexpr int kFusedWidth = 4;
+constexpr int kFusedHubMax = kTPB;
+constexpr int kFusedLongMax = 2048;
 constexpr int kBinMax = 7936;        // LDS bound: 62 KiB of staged products (+1 KiB starts)
 // Arrival counters of the sliced long rows: one uint32 per row, kCntStride apart (one
 // 64-B segment each, so the atomics of different rows never share a segment).

@@ -199,7 +199,7 @@ tpl_status tpl_dist_destroy(tpl_dist_t d) {
     hipSetDevice(d->ctx.device);
     if (d->ctx.stream) hipStreamSynchronize(d->ctx.stream);
     delete d;
-  });
+  }, true);
 }
 
 tpl_status tpl_dist_op_create_csr(tpl_dist_t d, int64_t n_global, const int64_t* starts,

@@ -1,0 +1,333 @@
+// tpl_k_p2_fused.hip — k_p2_hub and k_p2_rows: every step of pass two in two launches, for
+// a layout whose rows decouple once the long-row cache holds the long rows' sums (tpl_layout.h
+// FusedP2). Map of the device sources: tpl_kernels.hip.
+//
+// Pass two's recurrence for row i is
+//   v_{j+1}[i] = (((A v_j)_i - beta_{j-1} v_{j-1}[i]) - alpha_j v_j[i]) * (1 / beta_j),
+//   x[i] += y_j v_{j+1}[i],
+// and only (A v_j)_i couples rows. The cache (tpl_op.h SolverState::d_ycache) holds (A v_j)_r
+// of every long row r for every step pass one took, so a long row's whole history follows
+// from its own cache column and the step records; a CLOSED short row (every column a long
+// row or the row itself) needs only the long rows' v_j; the few OPEN rows and the long rows
+// they reference — the hub set H, at most kFusedHubMax rows — step together in one workgroup.
+//   k_p2_hub   one thread per long row: v_j[r] replaces the sum in the cache row of step j;
+//              one more workgroup owns H (its rows' only reader and writer in the cache) and
+//              exchanges v_j through LDS, one barrier per step.
+//   k_p2_rows  one workgroup per short chunk: a thread keeps its rows' entries, v and x in
+//              registers; per step the workgroup stages the long rows' v_j from the cache row
+//              into LDS (double-buffered: step j + 1's loads are issued before step j's
+//              arithmetic) and the rows gather from there.
+// No workgroup waits on another: the only dependency between workgroups is the kernel
+// boundary between the two launches.
+//
+// Bits: a row's sum is short_chunk_w's (s = 0; s += a_k x_k in entry order, padding adds
+// -0.0; the gather scale is 1) or the cached long-row sum, and its epilogue is
+// EpiPass2R::apply's operations in their order. x is kept in a register and takes one term per
+// step — the grouped flush of the step launches (tpl::p2_flush) adds the same terms in the
+// same order, so the roundings are the same. Both kernels stop at steps_taken - 1, which is
+// where the host schedule (and the one-graph schedule plus k_p2_tail) ends.
+#include "tpl_klaunch.h"
+
+namespace tpl {
+
+constexpr int kHubAhead = 8;  // steps a long row's cache and record loads run ahead of its chain
+
+struct FusedP2Args {
+  // the hub set (k_p2_hub's last workgroup)
+  const int32_t* h_row;
+  const int32_t* h_ent;
+  const double* h_val;
+  int32_t n_open, n_hub;
+  // both kernels
+  double* ycache;        // n_long doubles per step: sums in, v_j out (k_p2_hub); v_j (k_p2_rows)
+  const double* rec;     // DevState::p2c: 8 doubles per step (EpiPass2R)
+  const int32_t* flags;  // DevState::flags
+  const double* v1;
+  double* x;
+  int64_t n;
+  int32_t n_long;
+  int32_t steps;         // > 0: the steps taken; 0: flags[2] (nothing after an error, flags[1],
+                         // or when the device handed f(T_k) back, flags[4]: the host's pass
+                         // two follows and needs the sums)
+  // k_p2_rows: the short chunks (CsrDev)
+  const void* s_col;
+  const void* s_val;
+  const int32_t* s_cbase;
+  const int32_t* c_base;
+  const int32_t* c_width;
+  int32_t n_short, s_width, val_i8, s_col16;
+};
+
+__device__ __forceinline__ int fused_steps(const FusedP2Args& a) {
+  if (a.steps > 0) return a.steps;
+  return a.flags[1] || a.flags[4] ? 0 : a.flags[2];
+}
+
+// One step of one row (EpiPass2R::apply): s = (A v_j)_i, cv = the step's record, lane-wise
+// (lane l of the wave holds field l & 7). vp is 0.0 at j = 1, where the record's beta is 0.
+__device__ __forceinline__ void fused_step(double s, double cv, double& vc, double& vp, double& xv) {
+  const double beta_sub = readlane_f64(cv, 0), alpha = readlane_f64(cv, 1);
+  const double invb = readlane_f64(cv, 2), ycoef = readlane_f64(cv, 3);
+  double w = s - beta_sub * vp;
+  w = w - alpha * vc;
+  const double vn = w * invb;
+  xv = xv + ycoef * vn;
+  vp = vc;
+  vc = vn;
+}
+
+// Grid: [ceil(n_long / 256) long-row workgroups][the hub workgroup, if n_hub > 0].
+__global__ __launch_bounds__(kTPB) void k_p2_hub(FusedP2Args a) {
+  __shared__ double vh[2][kTPB];
+  const int steps = fused_steps(a);
+  if (steps < 2) return;  // uniform over the grid
+  const int last = steps - 1;
+  const int t = threadIdx.x;
+  const int nl = a.n_long;
+  const int64_t first_long = a.n - nl;
+  const int n_lb = (nl + kTPB - 1) / kTPB;
+  const bool hub = (int)blockIdx.x >= n_lb;  // uniform per workgroup
+  // this thread's row: a long row (its sums come from cache column lc), or an open row of H
+  bool live, open = false;
+  int lc;
+  int64_t row;
+  int ent[kFusedWidth];
+  double av[kFusedWidth];
+#pragma unroll
+  for (int k = 0; k < kFusedWidth; ++k) {
+    ent[k] = -1;
+    av[k] = 0.0;
+  }
+  if (hub) {
+    live = t < a.n_hub;
+    open = t < a.n_open;
+    row = a.h_row[clampi(t, a.n_hub - 1)];
+    lc = open ? 0 : clampi((int)(row - first_long), nl - 1);
+    if (open) {
+#pragma unroll
+      for (int k = 0; k < kFusedWidth; ++k) {
+        ent[k] = a.h_ent[t * kFusedWidth + k];
+        av[k] = a.h_val[t * kFusedWidth + k];
+      }
+    }
+  } else {
+    const int l = blockIdx.x * kTPB + t;
+    lc = clampi(l, nl - 1);
+    row = first_long + lc;
+    live = l < nl;
+    // H's long rows belong to the hub workgroup (h_row[n_open ..] ascending; a few at most)
+    for (int h = a.n_open; h < a.n_hub; ++h) live = live && a.h_row[h] != (int32_t)row;
+  }
+  double vc = a.v1[row], vp = 0.0, xv = a.x[row];
+  // the sums and records of the next kHubAhead steps: they do not depend on the chain
+  double yb[kHubAhead], cb[kHubAhead];
+#pragma unroll
+  for (int u = 0; u < kHubAhead; ++u) {
+    const int jj = clampi(1 + u, last);
+    yb[u] = a.ycache[(size_t)(jj - 1) * nl + lc];
+    cb[u] = a.rec[8 * (size_t)jj + (t & 7)];
+  }
+  for (int j0 = 1; j0 <= last; j0 += kHubAhead) {
+#pragma unroll
+    for (int u = 0; u < kHubAhead; ++u) {
+      const int j = j0 + u;
+      double s = yb[u];
+      const double cv = cb[u];
+      const int jn = clampi(j + kHubAhead, last);
+      yb[u] = a.ycache[(size_t)(jn - 1) * nl + lc];
+      cb[u] = a.rec[8 * (size_t)jn + (t & 7)];
+      if (j > last) break;  // uniform
+      if (live && !open) a.ycache[(size_t)(j - 1) * nl + lc] = vc;  // v_j[r] in the sum's place
+      if (hub) {
+        double* vb = vh[j & 1];
+        vb[t] = vc;
+        __syncthreads();
+        if (open) {  // short_chunk_w's sum over the row's entries
+          s = 0.0;
+#pragma unroll
+          for (int k = 0; k < kFusedWidth; ++k) {
+            const double prod = av[k] * vb[ent[k] < 0 ? 0 : ent[k]];
+            s = s + (ent[k] >= 0 ? prod : -0.0);
+          }
+        }
+      }
+      fused_step(s, cv, vc, vp, xv);
+    }
+  }
+  if (live) st_out(a.x + row, xv);
+}
+
+// Entry e of the short chunks as stored (tpl_kcommon.h col_at / val_at), formats at run time:
+// the entries are read once per solve.
+__device__ __forceinline__ int fused_col(const FusedP2Args& a, int e, int cbase) {
+  if (a.s_col16) {
+    const int off = reinterpret_cast<const uint16_t*>(a.s_col)[e];
+    return off == 0xFFFF ? -1 : cbase + off;
+  }
+  return reinterpret_cast<const int32_t*>(a.s_col)[e];
+}
+__device__ __forceinline__ double fused_val(const FusedP2Args& a, int e) {
+  if (a.val_i8) return (double)reinterpret_cast<const int8_t*>(a.s_val)[e];
+  return reinterpret_cast<const double*>(a.s_val)[e];
+}
+
+// Grid: one workgroup per short chunk. W: the widest chunk (1 .. kFusedWidth); NL: cache-row
+// loads per thread, ceil(n_long / 256). Dynamic LDS: 2 n_long doubles.
+template <int W, int NL>
+__global__ __launch_bounds__(kTPB) void k_p2_rows(FusedP2Args a) {
+  extern __shared__ double lds[];
+  const int steps = fused_steps(a);
+  if (steps < 2) return;  // uniform over the grid
+  const int last = steps - 1;
+  const int t = threadIdx.x;
+  const int chunk = blockIdx.x;
+  const int nl = a.n_long;
+  const int first_long = (int)(a.n - nl);
+  // the chunk's entries: width, base and order as short_chunk has them
+  const int wc = a.s_width > 0 ? a.s_width : a.c_width[chunk];
+  const int base = a.s_width > 0 ? chunk * kChunkRows * a.s_width : a.c_base[chunk];
+  const bool packed = a.s_width > 0 && packed_chunk_width(a.s_width);
+  const int cbase = a.s_col16 ? a.s_cbase[chunk] : 0;
+  int row[kRowsPerThread];
+  bool live[kRowsPerThread];
+  int li[kRowsPerThread][W];  // >= 0: long row's index; -1: padding; -2: the row itself
+  double av[kRowsPerThread][W];
+  double vc[kRowsPerThread], vp[kRowsPerThread], xv[kRowsPerThread];
+#pragma unroll
+  for (int q = 0; q < kRowsPerThread; ++q) {
+    const int p = chunk * kChunkRows + q * kTPB + t;
+    live[q] = p < a.n_short;
+    row[q] = clampi(p, a.n_short - 1);  // the long rows are last: position = row
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      // entries past the chunk's own width re-read its last one (masked below); a chunk of
+      // empty rows stores nothing: entry 0
+      const int kc = clampi(k, wc - 1);
+      const int e = wc <= 0 ? 0
+                    : packed ? base + t * (kRowsPerThread * wc) + q * wc + kc
+                             : base + kc * kChunkRows + q * kTPB + t;
+      const int c = fused_col(a, e, cbase);
+      av[q][k] = fused_val(a, e);
+      int idx = -1;
+      if (k < wc && c >= 0) {
+        if (c >= first_long) idx = c - first_long;
+        else if (c == row[q]) idx = -2;
+        else live[q] = false;  // an open row: the hub workgroup's
+      }
+      li[q][k] = idx;
+    }
+    vc[q] = a.v1[row[q]];
+    vp[q] = 0.0;
+    xv[q] = a.x[row[q]];
+  }
+  // step 1's cache row and record
+  double st[NL], cvn;
+#pragma unroll
+  for (int u = 0; u < NL; ++u) st[u] = a.ycache[clampi(t + u * kTPB, nl - 1)];
+  cvn = a.rec[8 + (t & 7)];
+  for (int j = 1; j <= last; ++j) {
+    double* vb = lds + (j & 1) * nl;
+#pragma unroll
+    for (int u = 0; u < NL; ++u)
+      if (t + u * kTPB < nl) vb[t + u * kTPB] = st[u];
+    const double cv = cvn;
+    // step j + 1's loads, in flight over this step's barrier, gathers and arithmetic
+    const int jn = clampi(j + 1, last);
+#pragma unroll
+    for (int u = 0; u < NL; ++u)
+      st[u] = a.ycache[(size_t)(jn - 1) * nl + clampi(t + u * kTPB, nl - 1)];
+    cvn = a.rec[8 * (size_t)jn + (t & 7)];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kRowsPerThread; ++q) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        const double g = vb[li[q][k] < 0 ? 0 : li[q][k]];
+        const double prod = av[q][k] * (li[q][k] == -2 ? vc[q] : g);
+        s = s + (li[q][k] != -1 ? prod : -0.0);  // padding adds -0.0: exact
+      }
+      fused_step(s, cv, vc[q], vp[q], xv[q]);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kRowsPerThread; ++q)
+    if (live[q]) st_out(a.x + row[q], xv[q]);
+}
+
+namespace launch {
+
+static FusedP2Args fused_args(const CsrDev& A, const DevState& S, const double* ycache,
+                              const double* v1, double* x, int steps) {
+  FusedP2Args a{};
+  a.ycache = const_cast<double*>(ycache);
+  a.rec = S.p2c;
+  a.flags = S.flags;
+  a.v1 = v1;
+  a.x = x;
+  a.n = A.n;
+  a.n_long = A.n_long;
+  a.steps = steps;
+  a.s_col = A.s_col;
+  a.s_val = A.s_val;
+  a.s_cbase = A.s_cbase;
+  a.c_base = A.c_base;
+  a.c_width = A.c_width;
+  a.n_short = A.n_short;
+  a.s_width = A.s_width;
+  a.val_i8 = A.val_i8;
+  a.s_col16 = A.s_col16;
+  return a;
+}
+
+hipError_t p2_fused_hub(const CsrDev& A, const DevState& S, const FusedP2Dev& H, double* ycache,
+                        const double* v1, double* x, int steps, hipStream_t s) {
+  if (A.n_long <= 0 || !A.s_identity || H.n_hub > kFusedHubMax || H.n_open > H.n_hub)
+    return hipErrorInvalidConfiguration;
+  FusedP2Args a = fused_args(A, S, ycache, v1, x, steps);
+  a.h_row = H.h_row;
+  a.h_ent = H.h_ent;
+  a.h_val = H.h_val;
+  a.n_open = H.n_open;
+  a.n_hub = H.n_hub;
+  const int grid = (A.n_long + kTPB - 1) / kTPB + (H.n_hub > 0 ? 1 : 0);
+  hipLaunchKernelGGL(k_p2_hub, dim3(grid), dim3(kTPB), 0, s, a);
+  return hipGetLastError();
+}
+
+template <int W, int... NLs>
+static bool rows_nl(int nloads, const FusedP2Args& a, int grid, size_t lds, hipStream_t s,
+                    std::integer_sequence<int, NLs...>) {
+  auto one = [&](auto NL) {
+    if (nloads != decltype(NL)::value + 1) return false;
+    hipLaunchKernelGGL((k_p2_rows<W, decltype(NL)::value + 1>), dim3(grid), dim3(kTPB), lds, s, a);
+    return true;
+  };
+  return (one(std::integral_constant<int, NLs>{}) || ...);
+}
+
+hipError_t p2_fused_rows(const CsrDev& A, const DevState& S, const double* ycache,
+                         const double* v1, double* x, int steps, hipStream_t s) {
+  if (A.n_long <= 0 || A.n_long > kFusedLongMax || !A.s_identity)
+    return hipErrorInvalidConfiguration;
+  if (A.n_chunks <= 0) return hipSuccess;  // no short row
+  const FusedP2Args a = fused_args(A, S, ycache, v1, x, steps);
+  const size_t lds = 2 * (size_t)A.n_long * sizeof(double);
+  const int nloads = (A.n_long + kTPB - 1) / kTPB;
+  constexpr auto nls = std::make_integer_sequence<int, kFusedLongMax / kTPB>{};
+  // W: the widest chunk. A uniform layout has its width; per-chunk widths (s_width == 0)
+  // run the widest instance, each chunk masking the entries past its own width
+  const int w = A.s_width > 0 ? A.s_width : kFusedWidth;
+  bool ok = false;
+  switch (w) {
+    case 1: ok = rows_nl<1>(nloads, a, A.n_chunks, lds, s, nls); break;
+    case 2: ok = rows_nl<2>(nloads, a, A.n_chunks, lds, s, nls); break;
+    case 3: ok = rows_nl<3>(nloads, a, A.n_chunks, lds, s, nls); break;
+    case 4: ok = rows_nl<4>(nloads, a, A.n_chunks, lds, s, nls); break;
+    default: break;
+  }
+  return ok ? hipGetLastError() : hipErrorInvalidConfiguration;
+}
+
+} // namespace launch
+} // namespace tpl

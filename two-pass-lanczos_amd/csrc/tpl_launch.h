@@ -41,6 +41,23 @@ hipError_t p2_cached(const CsrDev& A, const DevState& S, const double* xsrc, con
                      const double* v_prev, double* v_next, double* x, double* Vcol,
                      const double* ycache, const int32_t* lrow, int j, int nflush,
                      hipStream_t s);
+// The fused pass two (tpl_k_p2_fused.hip), after p2_init and p2_coefs: every step of pass two
+// in two launches, for a layout whose rows decouple (tpl_layout.h FusedP2) with the long rows
+// last. ycache holds (A v_j)_r of every long row for the steps pass one took (row j - 1:
+// step j); p2_fused_hub steps the long rows (and the hub set: h_row / h_ent / h_val, n_open
+// open rows of n_hub members) and leaves v_j[r] in the cache in place of the sums;
+// p2_fused_rows steps the closed short rows from them. steps > 0: the steps taken; 0: read
+// them (and the error flag) from the device state, as k_p2_tail does. v1, x: what p2_init
+// wrote; x gets the result.
+struct FusedP2Dev {
+  const int32_t *h_row, *h_ent;
+  const double* h_val;
+  int32_t n_open, n_hub;
+};
+hipError_t p2_fused_hub(const CsrDev& A, const DevState& S, const FusedP2Dev& H, double* ycache,
+                        const double* v1, double* x, int steps, hipStream_t s);
+hipError_t p2_fused_rows(const CsrDev& A, const DevState& S, const double* ycache,
+                         const double* v1, double* x, int steps, hipStream_t s);
 // the batch sibling (k_bp2_cached, tpl_k_batch_p2_cached.hip): step j of a group of nb
 // columns (the other batch launchers: tpl_batch.h) with the long rows' nb sums read from
 // `ycrow`, the step's row of the group's long-row cache (n_long x nb, a row's sums adjacent)

@@ -46,6 +46,61 @@ int32_t short_row_threshold(int64_t n, const std::vector<int32_t>& rp, int reque
   return std::max<int32_t>(4, std::min<int32_t>(kShortRowMax, 2 * median));
 }
 
+FusedP2 classify_fused_p2(int64_t n, const int32_t* rp, const int32_t* col, const double* val,
+                          int32_t T, int64_t long_from) {
+  FusedP2 f;
+  auto is_long = [&](int64_t i) { return long_from >= 0 ? i >= long_from : rp[i + 1] - rp[i] > T; };
+  int64_t n_long = 0;
+  int32_t widest = 0;
+  std::vector<int32_t> open;
+  for (int64_t i = 0; i < n; ++i) {
+    if (is_long(i)) {
+      ++n_long;
+      continue;
+    }
+    widest = std::max<int32_t>(widest, rp[i + 1] - rp[i]);
+    bool closed = true;
+    for (int32_t q = rp[i]; q < rp[i + 1] && closed; ++q)
+      closed = col[q] == i || is_long(col[q]);
+    if (!closed) open.push_back((int32_t)i);
+  }
+  f.n_open = (int64_t)open.size();
+  // H's long rows: those the open rows reference, ascending
+  std::vector<int32_t> hub_long;
+  bool cols_in_h = true;
+  if (f.n_open <= kFusedHubMax) {
+    for (const int32_t i : open)
+      for (int32_t q = rp[i]; q < rp[i + 1]; ++q) {
+        const int32_t c = col[q];
+        if (is_long(c)) hub_long.push_back(c);
+        else if (c != i) cols_in_h = cols_in_h && std::binary_search(open.begin(), open.end(), c);
+      }
+    std::sort(hub_long.begin(), hub_long.end());
+    hub_long.erase(std::unique(hub_long.begin(), hub_long.end()), hub_long.end());
+  }
+  f.n_hub = f.n_open + (int64_t)hub_long.size();
+  f.eligible = n_long > 0 && n_long <= kFusedLongMax && widest <= kFusedWidth &&
+               f.n_open <= kFusedHubMax && f.n_hub <= kFusedHubMax && cols_in_h;
+  if (!f.eligible) return f;
+  f.h_row = open;
+  f.h_row.insert(f.h_row.end(), hub_long.begin(), hub_long.end());
+  auto h_of = [&](int32_t c) {
+    if (is_long(c))
+      return (int32_t)(f.n_open + (std::lower_bound(hub_long.begin(), hub_long.end(), c) - hub_long.begin()));
+    return (int32_t)(std::lower_bound(open.begin(), open.end(), c) - open.begin());
+  };
+  f.h_ent.assign((size_t)f.n_open * kFusedWidth, -1);
+  if (val) f.h_val.assign((size_t)f.n_open * kFusedWidth, 0.0);
+  for (int64_t h = 0; h < f.n_open; ++h) {
+    const int32_t i = open[h];
+    for (int32_t q = rp[i]; q < rp[i + 1]; ++q) {
+      f.h_ent[h * kFusedWidth + (q - rp[i])] = h_of(col[q]);
+      if (val) f.h_val[h * kFusedWidth + (q - rp[i])] = val[q];
+    }
+  }
+  return f;
+}
+
 std::vector<int32_t> locality_order(int64_t n, const std::vector<int32_t>& rp,
                                     const std::vector<int32_t>& col, const SchedParams& sp) {
   const int32_t T = short_row_threshold(n, rp, sp.short_row_max);
@@ -452,6 +507,9 @@ Layout build_layout(int64_t n, int64_t n_glob, const std::vector<int32_t>& rp,
   // 200: 512 rows 2.50 ms per solve, 1024 2.52, 2048 2.54; the headline 500k: 2048 9.93,
   // 1024 9.98, 512 10.42 — profiles/r03_small_n_lab.txt)
   elem_geometry(n, sp, L.G2, L.E);
+  // the fused pass two's row classes (single GPU: columns are row indices)
+  if (!cmap.table && !cmap.starts && n == n_glob)
+    L.fp2 = classify_fused_p2(n, rp.data(), col.data(), val.data(), T, sp.long_from);
   return L;
 }
 

@@ -36,6 +36,29 @@ struct SchedParams {
                                     // the others
 };
 
+// Row classes of the fused pass two (tpl_k_p2_fused.hip). With the long-row cache holding
+// (A v_j)_r of every long row r for every step, a long row's whole pass-two history follows
+// from its own cache column, and so does that of a CLOSED short row — every column a long
+// row or the row itself — once the long rows' v_j are known. Any other short row is OPEN.
+// The hub set H: the open rows plus the long rows they reference; one workgroup steps H
+// with one thread per row. Eligible: some long row, every short row at most kFusedWidth
+// entries wide, at most kFusedLongMax long rows (their v_j are staged in LDS twice over),
+// |H| <= kFusedHubMax, and every column of an open row in H (always so for a symmetric
+// pattern). Whether the long rows are the last rows is the operator's matter (s_identity).
+struct FusedP2 {
+  bool eligible = false;
+  int64_t n_open = 0, n_hub = 0;
+  // the hub workgroup's tables (eligible only): member h's row (open rows first, each set
+  // ascending), and the open rows' entries in their row order, kFusedWidth per row: the
+  // column's index in H (-1: padding) and the value
+  std::vector<int32_t> h_row, h_ent;
+  std::vector<double> h_val;
+};
+// Classifies the rows of a CSR matrix (columns ascending per row; val may be nullptr: no
+// h_val) whose rows longer than T are the long rows (long_from >= 0: rows [long_from, n)).
+FusedP2 classify_fused_p2(int64_t n, const int32_t* rp, const int32_t* col, const double* val,
+                          int32_t T, int64_t long_from);
+
 // Host copy of the SpMV layout (tpl_device.h).
 struct Layout {
   std::vector<int32_t> srows;       // short rows, ascending
@@ -60,6 +83,7 @@ struct Layout {
   int G2 = 1;
   int64_t E = 512;
   int32_t s_win = 0, s_win_max = 0;  // short-chunk column window (tpl_device.h)
+  FusedP2 fp2;                      // row classes of the fused pass two (above)
 };
 
 // Column index as stored on the device: the identity on one GPU; with the rows

@@ -38,11 +38,14 @@ namespace tpl {
                   std::string(#expr) + ": " + hipGetErrorString(e_));                       \
   } while (0)
 
+// keep_error: success leaves the thread's recorded error as it is (the destroy entry
+// points: a binding's finalizer may run between a failed call and the caller's
+// tpl_last_error_detail, and must not wipe what that call recorded).
 template <class F>
-tpl_status guarded(F&& f) {
+tpl_status guarded(F&& f, bool keep_error = false) {
   try {
     f();
-    set_last_error("");
+    if (!keep_error) set_last_error("");
     return TPL_OK;
   } catch (const Error& e) {
     // a failed HIP call leaves its status as the runtime's "last error", which the next
@@ -69,6 +72,9 @@ struct LayoutBufs {
   unsigned int* d_Pcnt = nullptr;
   int32_t *d_perm = nullptr, *d_iperm = nullptr;  // locality order (empty perm: nullptr)
   double* d_stage = nullptr;        // one host-order vector (host uploads / downloads)
+  // the fused pass two's hub tables (Layout::fp2; nullptr: not eligible, or no open row)
+  int32_t *d_hrow = nullptr, *d_hent = nullptr;
+  double* d_hval = nullptr;
 };
 
 // The solver state of an operator, sized for kcap steps: ensure_state replaces the set.
@@ -209,6 +215,12 @@ struct tpl_op_s {
   // and runs the full kernels
   bool use_long_cache = false;
   bool last_long_cache = false;     // the last pass two the operator ran read the cache
+  // fused pass two (tpl_op_set_fused_pass_two): 0 off, 2 auto — whenever fused_p2 (below) holds
+  int fused_p2 = 2;
+  // the running call is tpl_lanczos_two_pass and asked for this many steps (LongCacheScope;
+  // 0: any other entry point)
+  size_t fused_call_k = 0;
+  bool last_fused_p2 = false;       // the last pass two the operator ran was the fused one
   int64_t reorth_second = 0;        // second Gram-Schmidt passes of the last reorth solve
   // locality order (single GPU, tpl_op_set_reorder): the device works on P A P^T; vectors
   // cross the boundary through a gather (internal i <- caller's perm[i], back via iperm).
@@ -266,6 +278,14 @@ uint64_t long_cache_rows(int mode, uint64_t budget_bytes, int64_t n, int64_t n_l
 // single column, and of a batch group.
 inline size_t long_cache_steps(const tpl_op_s* op) {
   return op->use_long_cache ? op->st.yrows : 0;
+}
+// Pass two of the running call runs fused (k_p2_hub + k_p2_rows, tpl_k_p2_fused.hip) instead
+// of its step launches: the mode is on, the layout's rows decouple (Layout::fp2) with the long
+// rows last, the call is a single-GPU tpl_lanczos_two_pass, and the long-row cache holds every
+// step the call asked for.
+inline bool fused_p2(const tpl_op_s* op) {
+  return op->fused_p2 != 0 && op->lay.fp2.eligible && op->lay.s_identity && !op->dist &&
+         op->fused_call_k > 0 && long_cache_steps(op) >= op->fused_call_k;
 }
 inline size_t batch_cache_steps(const tpl_op_s* op) {
   return op->use_long_cache ? op->bat.yrows : 0;

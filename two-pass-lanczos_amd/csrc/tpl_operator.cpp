@@ -108,6 +108,7 @@ void free_bufs(tpl_op_s* op, LayoutBufs& b) {
   dev_free(op, b.d_cwidth), dev_free(op, b.d_bcbase), dev_free(op, b.d_bhdr);
   dev_free(op, b.d_bseg), dev_free(op, b.d_P), dev_free(op, b.d_Pcnt);
   dev_free(op, b.d_perm), dev_free(op, b.d_iperm), dev_free(op, b.d_stage);
+  dev_free(op, b.d_hrow), dev_free(op, b.d_hent), dev_free(op, b.d_hval);
 }
 
 // A layout (and its row order) into a fresh set of device buffers.
@@ -117,6 +118,9 @@ void upload_layout(tpl_op_s* op, const Layout& L, const std::vector<int32_t>& pe
   upload(op, &nb.d_iperm, iperm);
   if (!perm.empty()) dev_alloc(op, &nb.d_stage, perm.size() * sizeof(double));
   upload(op, &nb.d_srows, L.srows);
+  upload(op, &nb.d_hrow, L.fp2.h_row);
+  upload(op, &nb.d_hent, L.fp2.h_ent);
+  upload(op, &nb.d_hval, L.fp2.h_val);
   // entries in the device order (tpl_device.h kPackedEntries; positions unchanged)
   const bool pack_s = packed_chunk_width(L.s_width);
   auto sidx = [&](int64_t i) { return pack_s ? packed_chunk_index(i, L.s_width) : i; };
@@ -772,7 +776,7 @@ tpl_status tpl_ctx_destroy(tpl_ctx_t ctx) {
     hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     delete ctx;
-  });
+  }, true);
 }
 
 tpl_status tpl_ctx_synchronize(tpl_ctx_t ctx) {
@@ -804,7 +808,7 @@ tpl_status tpl_op_destroy(tpl_op_t op) {
       hipStreamSynchronize(op->stream);
     }
     delete op;
-  });
+  }, true);
 }
 
 int64_t tpl_op_nrows(tpl_op_t op) { return op ? op->part.n : -1; }
@@ -814,7 +818,32 @@ int tpl_op_flags(tpl_op_t op) {
   return (op->dist ? 1 : 0) | (op->eager ? 2 : 0) | (op->lay.val_i8 ? 4 : 0) |
          (op->lay.s_col16 ? 8 : 0) | (op->lay.b_col16 ? 16 : 0) | (op->last_one_graph ? 32 : 0) |
          (!op->perm.empty() || op->part.local_order ? 64 : 0) | (op->pb_ld > 0 ? 128 : 0) |
-         (op->last_long_cache ? 256 : 0);
+         (op->last_long_cache ? 256 : 0) | (op->last_fused_p2 ? 512 : 0);
+}
+
+tpl_status tpl_op_set_fused_pass_two(tpl_op_t op, int mode) {
+  return guarded([&] {
+    if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
+    if (mode != 0 && mode != 2) fail(TPL_ERR_INVALID_ARGUMENT, "fused pass-two mode must be 0 or 2");
+    if (!op->plan_only) {  // a host-only plan keeps the mode and has nothing to drop
+      set_device(op);
+      sync_checked(op);
+      drop_graphs(op);
+    }
+    op->fused_p2 = mode;
+  });
+}
+int tpl_fused_pass_two_rows(int64_t n, const int64_t* row_ptr, const int32_t* col_idx,
+                            int short_row_max, int* eligible, int64_t* n_open, int64_t* n_hub) {
+  if (n < 0 || !row_ptr || (row_ptr[n] > 0 && !col_idx) || row_ptr[n] >= INT32_MAX) return -1;
+  std::vector<int32_t> rp((size_t)n + 1);
+  for (int64_t i = 0; i <= n; ++i) rp[i] = (int32_t)row_ptr[i];
+  const tpl::FusedP2 f = tpl::classify_fused_p2(
+      n, rp.data(), col_idx, nullptr, tpl::short_row_threshold(n, rp, short_row_max), -1);
+  if (eligible) *eligible = f.eligible ? 1 : 0;
+  if (n_open) *n_open = f.n_open;
+  if (n_hub) *n_hub = f.n_hub;
+  return 0;
 }
 
 tpl_status tpl_op_set_long_cache(tpl_op_t op, int mode, uint64_t budget_bytes) {

@@ -26,6 +26,8 @@ enum GraphKind {
                       // number of steps: one graph per (steps, NB, m)
   kGLongCache = 64,   // + this: the sequence stores / reads the long-row cache (a two-pass
                       // solve with the cache on for it; other kernels, other graphs)
+  kGFusedP2 = 128,    // + this: pass two is the fused one (k_p2_hub, k_p2_rows) in place of
+                      // the step launches (and of k_p2_tail)
 };
 // What tells one pass-one sequence (and its graph) from another, beside k: the basis is
 // stored (the standard pass), T_k's LU is eliminated as it goes (a device inv follows:
@@ -39,7 +41,9 @@ inline double* cache_row(const tpl_op_s* op, int j) {
   return (size_t)j <= long_cache_steps(op)
              ? op->st.d_ycache + (size_t)(j - 1) * op->lay.lrows.size() : nullptr;
 }
-inline int graph_cache_kind(const tpl_op_s* op) { return long_cache_steps(op) ? kGLongCache : 0; }
+inline int graph_cache_kind(const tpl_op_s* op) {
+  return long_cache_steps(op) ? kGLongCache | (fused_p2(op) ? kGFusedP2 : 0) : 0;
+}
 // The same for a batch group of nb columns: the row of step j in the group's own cache.
 inline double* batch_cache_row(const tpl_op_s* op, int j, int nb) {
   return (size_t)j <= batch_cache_steps(op)
@@ -186,6 +190,19 @@ static void enqueue_pass2_steps(tpl_op_s* op, size_t steps, double* Vout) {
     }
   }
 }
+// The fused pass two (tpl_op.h fused_p2), after the prologue: every step in two launches.
+// steps > 0: the steps taken (the host knows them); 0: the device-held count (one-graph
+// solve), whose pending x terms need no k_p2_tail — both kernels run the host schedule.
+static void enqueue_pass2_fused(tpl_op_s* op, size_t steps) {
+  const CsrDev A = csr_dev(op);
+  const FusedP2& f = op->lay.fp2;
+  const launch::FusedP2Dev H{op->bufs.d_hrow, op->bufs.d_hent, op->bufs.d_hval, (int32_t)f.n_open,
+                             (int32_t)f.n_hub};
+  HIPCHK(launch::p2_fused_hub(A, op->st.S, H, op->st.d_ycache, op->V2[1], op->x, (int)steps,
+                              op->stream));
+  HIPCHK(launch::p2_fused_rows(A, op->st.S, op->st.d_ycache, op->V2[1], op->x, (int)steps,
+                               op->stream));
+}
 void enqueue_pass2(tpl_op_s* op, size_t steps, double* Vout) {
   enqueue_pass2_init(op, steps, Vout);
   enqueue_pass2_steps(op, steps, Vout);
@@ -269,15 +286,22 @@ static void run_pass1_graph(tpl_op_s* op, size_t k, int props) {
 // and events bracket the graph of the steps - 1 step launches (tpl_op_pass_timing).
 void run_pass2(tpl_op_s* op, size_t steps) {
   op->last_long_cache = steps >= 2 && long_cache_steps(op) > 0;
+  const bool fused = fused_p2(op);
+  op->last_fused_p2 = steps >= 2 && fused;
+  auto enqueue_steps = [&] {
+    if (fused) enqueue_pass2_fused(op, steps);
+    else enqueue_pass2_steps(op, steps, nullptr);
+  };
   if (!op->timing) {
-    run_graph(op, kGPass2 + graph_cache_kind(op), steps,
-              [&] { enqueue_pass2(op, steps, nullptr); });
+    run_graph(op, kGPass2 + graph_cache_kind(op), steps, [&] {
+      enqueue_pass2_init(op, steps, nullptr);
+      enqueue_steps();
+    });
     return;
   }
   enqueue_pass2_init(op, steps, nullptr);
   HIPCHK(hipEventRecord(op->tev[2], op->stream));
-  run_graph(op, kGPass2Steps + graph_cache_kind(op), steps,
-            [&] { enqueue_pass2_steps(op, steps, nullptr); });
+  run_graph(op, kGPass2Steps + graph_cache_kind(op), steps, enqueue_steps);
   HIPCHK(hipEventRecord(op->tev[3], op->stream));
   op->p2_launches = (int64_t)steps - 1;
 }
@@ -438,13 +462,19 @@ void run_two_pass_dev(tpl_op_s* op, size_t k, int f) {
   const int elim = f == kDevInv ? kP1Elim : 0;  // T_k's LU eliminated during pass one
   const int ck = graph_cache_kind(op);
   op->last_long_cache = k >= 2 && ck != 0;
+  const bool fused = fused_p2(op);
+  op->last_fused_p2 = k >= 2 && fused;
   if (!op->timing) {
     op->p1_samples = 0;  // the untimed graph records no launch stamps
     run_graph(op, kGTwoPassDev + ck, key, [&] {
       enqueue_pass1(op, k, elim | (ck ? kP1Cache : 0));
       enqueue_ftk_dev(op, k, f);
-      enqueue_pass2_dyn_steps(op, k);
-      enqueue_pass2_tail(op);
+      if (fused) {
+        enqueue_pass2_fused(op, 0);
+      } else {
+        enqueue_pass2_dyn_steps(op, k);
+        enqueue_pass2_tail(op);
+      }
     });
     return;
   }
@@ -459,9 +489,12 @@ void run_two_pass_dev(tpl_op_s* op, size_t k, int f) {
   HIPCHK(hipEventRecord(op->tev[1], op->stream));
   run_graph(op, kGDevFtk, key, [&] { enqueue_ftk_dev(op, k, f); });
   HIPCHK(hipEventRecord(op->tev[2], op->stream));
-  run_graph(op, kGPass2Dyn + ck, k, [&] { enqueue_pass2_dyn_steps(op, k); });
+  run_graph(op, kGPass2Dyn + ck, k, [&] {
+    if (fused) enqueue_pass2_fused(op, 0);
+    else enqueue_pass2_dyn_steps(op, k);
+  });
   HIPCHK(hipEventRecord(op->tev[3], op->stream));
-  enqueue_pass2_tail(op);
+  if (!fused) enqueue_pass2_tail(op);
   op->p2_launches = (int64_t)k - 1;
 }
 

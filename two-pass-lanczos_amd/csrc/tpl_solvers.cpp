@@ -155,11 +155,18 @@ void pass_two_one(tpl_op_s* op, const double* b, const double* alphas, size_t n_
 // so every other pass runs the full kernels and never reads a row another solve wrote.
 struct LongCacheScope {
   tpl_op_s* op;
-  LongCacheScope(tpl_op_s* o, unsigned bit) : op(o) {
+  // k: the steps a tpl_lanczos_two_pass call asked for (its pass two may run fused:
+  // tpl_op.h fused_p2); 0 from every other solver
+  LongCacheScope(tpl_op_s* o, unsigned bit, size_t k = 0) : op(o) {
     op->use_long_cache = (op->long_cache_solvers & bit) != 0;
     op->last_long_cache = false;
+    op->last_fused_p2 = false;
+    op->fused_call_k = k;
   }
-  ~LongCacheScope() { op->use_long_cache = false; }
+  ~LongCacheScope() {
+    op->use_long_cache = false;
+    op->fused_call_k = 0;
+  }
 };
 
 // Where a k-step solve evaluates f(T_k): on the device for the built-in inv / exp of an
@@ -312,7 +319,7 @@ tpl_status tpl_lanczos_two_pass(tpl_op_t op, const double* b, int64_t b_len, siz
     set_device(op);
     check_b(op, b, b_len);
     check_k(k);
-    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS);
+    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS, k);
     // the built-in inv / exp on the device: the whole solve one graph (pass one, f(T_k)
     // from the device alpha / beta, pass two), no host round trip between the passes
     const DevF dev_f = device_f(op, f, k);

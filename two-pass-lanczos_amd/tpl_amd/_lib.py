@@ -268,4 +268,9 @@ EXPORTED += ["tpl_dist_op_create_replicated", "tpl_op_local_rows", "tpl_dist_par
              "tpl_operand_key"]
 EXPORTED += ["tpl_op_set_long_cache", "tpl_long_cache_default_budget", "tpl_long_cache_rows"]
 EXPORTED += ["tpl_op_set_long_cache_solvers"]
+tpl_op_set_fused_pass_two = _sig("tpl_op_set_fused_pass_two", c_int, c_void_p, c_int)
+tpl_fused_pass_two_rows = _sig("tpl_fused_pass_two_rows", c_int, c_int64, c_void_p, c_void_p, c_int,
+                               ctypes.POINTER(c_int), ctypes.POINTER(c_int64),
+                               ctypes.POINTER(c_int64))
+EXPORTED += ["tpl_op_set_fused_pass_two", "tpl_fused_pass_two_rows"]
 EXPORTED += ["tpl_ftk_exp_t", "tpl_lanczos_two_pass_exp_times", "tpl_op_ftk_exp_times_device"]

@@ -76,6 +76,19 @@ def locality_order(a, short_row_max: int = -1, groups: int = 16):
     return perm[:n].copy() if applied.value else None
 
 
+def fused_pass_two_rows(a, short_row_max: int = -1):
+    """The fused pass two's verdict on matrix ``a`` (tpl_fused_pass_two_rows; host only):
+    (eligible, n_open, n_hub) — whether the row classes allow it, the open short rows, and
+    the size of the hub set."""
+    n, rp, ci, _ = _as_csr_arrays(a)
+    el, n_open, n_hub = ctypes.c_int(), c_int64(), c_int64()
+    rc = _lib.tpl_fused_pass_two_rows(n, rp.ctypes.data, ci.ctypes.data, int(short_row_max),
+                                      byref(el), byref(n_open), byref(n_hub))
+    if rc != 0:
+        raise TplError(_lib.TPL_ERR_INVALID_ARGUMENT, "tpl_fused_pass_two_rows: bad arguments")
+    return bool(el.value), int(n_open.value), int(n_hub.value)
+
+
 def _is_torch_cuda(x) -> bool:
     return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
 
@@ -296,6 +309,13 @@ class HipCsrOp:
         LONG_CACHE_TWO_PASS_BATCH_MULTI. A remainder column follows the bit of the solver that
         was called. Results are bitwise the same whatever the mask."""
         check(_lib.tpl_op_set_long_cache_solvers(self._op, int(mask)))
+
+    def set_fused_pass_two(self, mode=2):
+        """Fused pass two of lanczos_two_pass (tpl_op_set_fused_pass_two): 0 / False off, 2
+        auto (default) — two launches for all of pass two's steps wherever the layout's rows
+        decouple and the long-row cache holds every step. Bitwise the same results either
+        way. flags() bit 9 tells whether the last pass two ran fused."""
+        check(_lib.tpl_op_set_fused_pass_two(self._op, int(mode)))
 
     def ftk_device(self, which: str, alphas, betas):
         """The device f(T_k) kernel alone ("inv" / "exp") on this operator's GPU:
