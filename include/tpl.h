@@ -343,6 +343,46 @@ tpl_status tpl_lanczos_pass_two_batch_multi(tpl_op_t op, const double* B, int64_
                                             size_t s, const double* alphas, const double* betas,
                                             size_t ld, const size_t* steps, const double* b_norms,
                                             const double* y, size_t m, double* x_out, int mem);
+/* exp(t_i A) b_c for the m times ts[0..m) and the s columns of B in one run: the batch-multi
+ * solve with every exp(t_i T_k) e_1 on the device. x_out is column-major n x (s m), result
+ * (c, i) at column (c m + i), as tpl_lanczos_two_pass_batch_multi's; on_device (s m entries
+ * at c m + i, or NULL): 1 where the device's y was used. Per group of four or two columns
+ * (the batch solve's grouping rule, no group padded): the lock-step pass one; then, unless
+ * the operator's device-f mode is 0 (tpl_op_set_device_ftk) or k > 1800, straight behind it
+ * on the stream ONE launch of k_ftk_exp_times_batch, one workgroup per (time, column), each
+ * column on its own device-held steps_c (tpl_lanczos_two_pass_exp_times's evaluation on the
+ * tridiagonal t_i * alphas_c, t_i * betas_c, with its accuracy and its hand-back rules); one
+ * synchronisation; then for each column c ascending the batch solve's zero-vector check and,
+ * for i ascending, tpl_ftk_exp_t on the host for every (c, i) the device handed back (in mode
+ * 0 or past k = 1800: for every (c, i)), only those columns being uploaded; then ONE pass two
+ * for the group's nb m results. A last single column runs tpl_lanczos_two_pass_exp_times's
+ * body on that b. m == 1 takes the same path.
+ * Parity, in bits: result (c, .) and on_device[c m + .] are what
+ * tpl_lanczos_two_pass_exp_times(op, b_c, k, ts, m) returns — result (c, i) is
+ * tpl_lanczos_pass_two on column c's decomposition with the y that was used; in mode 0 the
+ * whole result is tpl_lanczos_two_pass_batch_multi's with fs[i] = tpl_ftk_exp_t,
+ * f_users[i] = &ts[i]. Nothing depends on s, on m, on a column's position, on the other
+ * columns' contents (non-finite values included) or on the long-row cache mask; a column
+ * that breaks down at step j_c keeps steps_c = j_c for all its m results.
+ * Errors: those of tpl_lanczos_two_pass_batch_multi (the first failure ends the call with the
+ * single solve's error text and detail); NULL ts or a non-finite t_i:
+ * TPL_ERR_INVALID_ARGUMENT, before any device work; a partitioned operator:
+ * TPL_ERR_UNSUPPORTED; a host-only plan is refused as by every solver. tpl_op_flags bit 5
+ * reads 0 afterwards; the long-row cache follows the TPL_LONG_CACHE_TWO_PASS_BATCH_MULTI bit,
+ * the remainder column included; no live timing.
+ * Device memory: the operator's first call of this entry point or of
+ * tpl_op_ftk_exp_times_batch_device adds, beyond the batch-multi solve's buffers, exactly
+ * 1,024 bytes (the hand-back table: 4 x TPL_MULTI_MAX int32) and, where no exp-times call
+ * allocated them before, the 512 bytes of the times (TPL_MULTI_MAX doubles); a remainder
+ * column adds what tpl_lanczos_two_pass_exp_times adds. As many bytes of pinned host memory
+ * mirror the table.
+ * Measured, 500k headline, k = 500: s = 4, m = 4 takes 32.3 ms against 91.2 ms
+ * for tpl_lanczos_two_pass_batch_multi with exp_t closures (0.35), s = 2, m = 1 16.0 against
+ * 23.3 ms (0.69); no measured shape (s, m in (2,1) (2,4) (4,1) (4,4) (4,8), also at 50k arcs
+ * with k = 200) is slower than that baseline.                                         */
+tpl_status tpl_lanczos_two_pass_batch_exp_times(tpl_op_t op, const double* B, int64_t b_len,
+                                                size_t s, size_t k, const double* ts, size_t m,
+                                                double* x_out, int mem, int32_t* on_device);
 
 /* Where tpl_lanczos_two_pass evaluates the built-in f(T_k): mode 0 = host (two graphs
  * around the host call), 1 = device (the whole solve one graph), 2 = auto (default).
@@ -453,6 +493,19 @@ tpl_status tpl_op_ftk_device(tpl_op_t op, int which, const double* alphas, size_
 tpl_status tpl_op_ftk_exp_times_device(tpl_op_t op, const double* alphas, size_t n,
                                        const double* betas, const double* ts, size_t m,
                                        double* y_out, int32_t* on_device);
+/* The same for k_ftk_exp_times_batch alone, on a group of nb (2 or 4) tridiagonals: column c
+ * of alphas / betas at c ld, steps[c] rows of it in use (1 <= steps[c] <= min(ld, 1800); 0 or
+ * above ld: TPL_ERR_INVALID_ARGUMENT, above 1800: TPL_ERR_UNSUPPORTED), the m times
+ * ts[0..m) (1 <= m <= TPL_MULTI_MAX). Loads a group state as pass one leaves it
+ * (||b_c|| = 1, no error), runs the one launch and copies back: y_out (host, column-major
+ * ld x (nb m)) holds in column (c m + i) the steps[c] unscaled entries of exp(t_i T_c) e_1
+ * and zeros behind them; on_device[c m + i] = 0 where the kernel handed (c, i) back (that
+ * column then 0). Column (c m + i) and its entry are bitwise tpl_op_ftk_device(op, 1, ...)
+ * on t_i * alphas_c, t_i * betas_c.                                                    */
+tpl_status tpl_op_ftk_exp_times_batch_device(tpl_op_t op, const double* alphas,
+                                             const double* betas, size_t ld, const size_t* steps,
+                                             size_t nb, const double* ts, size_t m, double* y_out,
+                                             int32_t* on_device);
 
 /* ---- low-level API: src/algorithms/ -------------------------------------- */
 /* Per-step callback of lanczos_standard (LanczosCallback, src/algorithms/mod.rs:82-86):

@@ -5,6 +5,7 @@
  *   tpl::solvers::lanczos / lanczos_two_pass          src/solvers.rs:46-107, 133-175
  *   tpl::solvers::lanczos_two_pass_multi / lanczos_multi   (none: m functions, one Krylov run)
  *   tpl::solvers::lanczos_two_pass_exp_times               (none: exp(t_i A) b at m times)
+ *   tpl::solvers::lanczos_two_pass_batch_exp_times         (none: exp(t_i A) b_c, s columns)
  *   tpl::algorithms::lanczos_standard                 src/algorithms/lanczos.rs:55-156
  *   tpl::algorithms::lanczos_pass_one                 src/algorithms/lanczos_two_pass.rs:65-110
  *   tpl::algorithms::lanczos_pass_two[_with_basis]    src/algorithms/lanczos_two_pass.rs:128-166
@@ -573,6 +574,24 @@ inline Mat lanczos_two_pass_batch_multi(const HipCsrOp& op, const Mat& B, size_t
         throw LanczosError::parameter_mismatch("y_k_prime", (size_t)d.expected, c.rows);
       }
   detail::check(st);
+  return x;
+}
+// exp(t_i A) b_c for the times ts and the s columns of B (n x s) by one run
+// (tpl_lanczos_two_pass_batch_exp_times): per group of columns pass one in lock-step, every
+// exp(t_i T_k) e_1 of every column at once on the device (what it hands back runs the host
+// tpl_ftk_exp_t), one pass two. Column (c m + i) of the n x (s m) result is bitwise column i of
+// lanczos_two_pass_exp_times for B's column c; on_device, if given, is resized to s m:
+// entry (c m + i) is 1 where the device's y was used.
+inline Mat lanczos_two_pass_batch_exp_times(const HipCsrOp& op, const Mat& B, size_t k,
+                                            const std::vector<double>& ts,
+                                            std::vector<int32_t>* on_device = nullptr) {
+  if (B.rows != op.ncols()) throw LanczosError::dimension_mismatch(op.ncols(), B.rows);
+  const size_t m = ts.size();
+  Mat x(op.nrows(), B.cols * m);
+  if (on_device) on_device->assign(B.cols * m, 0);
+  detail::check(tpl_lanczos_two_pass_batch_exp_times(
+      op.handle(), B.data.data(), (int64_t)B.rows, B.cols, k, ts.data(), m, x.data.data(),
+      TPL_MEM_HOST, on_device ? on_device->data() : nullptr));
   return x;
 }
 }  // namespace solvers

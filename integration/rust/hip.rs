@@ -134,6 +134,13 @@ extern "C" {
     fn tpl_ftk_exp_t(alphas: *const f64, n_alphas: usize, betas: *const f64, n_betas: usize,
                      y_out: *mut f64, y_cap: usize, y_len: *mut usize, err_msg: *mut c_char,
                      err_cap: usize, user: *mut c_void) -> c_int;
+    fn tpl_lanczos_two_pass_batch_exp_times(op: *mut TplOp, B: *const f64, b_len: i64, s: usize,
+                                            k: usize, ts: *const f64, m: usize, x_out: *mut f64,
+                                            mem: c_int, on_device: *mut i32) -> c_int;
+    fn tpl_op_ftk_exp_times_batch_device(op: *mut TplOp, alphas: *const f64, betas: *const f64,
+                                         ld: usize, steps: *const usize, nb: usize,
+                                         ts: *const f64, m: usize, y_out: *mut f64,
+                                         on_device: *mut i32) -> c_int;
     fn tpl_lanczos_multi(op: *mut TplOp, b: *const f64, b_len: i64, k: usize,
                          fs: *const FtkFn, f_users: *mut *mut c_void, m: usize,
                          x_out: *mut f64, mem: c_int) -> c_int;
@@ -948,5 +955,35 @@ where
                                                    x.as_mut_ptr(), TPL_MEM_HOST))?;
         }
         Ok(column_major(&x, op.n, s * m))
+    })?
+}
+
+/// exp(t_i A) b_c for the times `ts` and the s columns of `b` (n x s) by ONE run (no reference
+/// counterpart): per group of columns pass one in lock-step, every exp(t_i T_k) e_1 of every
+/// column at once on the device (what it hands back runs the native host `tpl_ftk_exp_t`), one
+/// pass two. Returns the n x (s m) result, column (c m + i) = exp(ts[i] A) b_c — bitwise
+/// `lanczos_two_pass_exp_times` of `b`'s column c — and, per column of it, whether the device's
+/// y was used.
+pub fn lanczos_two_pass_batch_exp_times<O: HipOperand>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    k: usize,
+    ts: &[f64],
+    stack: &mut MemStack,
+) -> Result<(Mat<f64>, Vec<bool>), LanczosError> {
+    let _ = stack;
+    let (n, s) = (b.nrows(), b.ncols());
+    let bv: Vec<f64> = (0..n * s).map(|t| b[(t % n, t / n)]).collect();
+    let m = ts.len();
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n * s * m];
+        let mut on = vec![0i32; s * m];
+        let _g = op.lock.lock().unwrap();
+        unsafe {
+            check(tpl_lanczos_two_pass_batch_exp_times(op.op, bv.as_ptr(), n as i64, s, k,
+                                                       ts.as_ptr(), m, x.as_mut_ptr(),
+                                                       TPL_MEM_HOST, on.as_mut_ptr()))?;
+        }
+        Ok((column_major(&x, op.n, s * m), on.iter().map(|&v| v != 0).collect()))
     })?
 }

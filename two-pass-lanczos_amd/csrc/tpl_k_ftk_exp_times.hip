@@ -1,30 +1,12 @@
 // tpl_k_ftk_exp_times.hip — exp(t_i T_k) e_1 for m times at once (k_ftk_exp_times), between
 // the shared passes of tpl_lanczos_two_pass_exp_times. The body is tpl_kexp.h's, shared with
-// k_ftk_exp (tpl_k_ftk_exp.hip); tpl_kernels.hip's map of the device sources leaves this unit
+// k_ftk_exp (tpl_k_ftk_exp.hip), as are the source and destination types (ExpSrcTimes,
+// ExpDstTimes: every entry of T_k times t_i, rounded once); tpl_kernels.hip's map of the device sources leaves this unit
 // out (bench.py ties the committed headline profile to that file's bytes).
 #include "../../include/tpl.h"
 #include "tpl_kexp.h"
 
 namespace tpl {
-
-namespace {
-// t T_k: every entry times t, one rounding (RN(t alpha_j), RN(t beta_j) — the arrays the host
-// built-in tpl_ftk_exp_t forms), before anything else uses it. The build's -ffp-contract=off
-// keeps the product out of the subtractions that follow (t alpha - c stays two roundings).
-struct ExpSrcTimes {
-  const double *al, *be;
-  double t;
-  __device__ __forceinline__ double alpha(int i) const { return t * al[i]; }
-  __device__ __forceinline__ double beta(int i) const { return t * be[i]; }
-};
-struct ExpDstTimes {  // a column of the coefficient table and the time's hand-back entry
-  double* y_;
-  int32_t* back;
-  __device__ __forceinline__ void y(int i, double v) const { y_[i] = v; }
-  __device__ __forceinline__ void hand_back() const { *back = 1; }
-  __device__ __forceinline__ void kept() const { *back = 0; }
-};
-} // namespace
 
 // Workgroup i: k_ftk_exp's evaluation on t_i T_k — column i of Y (columns ldy apart), times
 // ||b|| when `scale`, and back[i] = 0; or, where k_ftk_exp would hand the case back, a zero

@@ -1,6 +1,7 @@
 // tpl_kexp.h — the body of the device exp(T) e_1, shared by k_ftk_exp (tpl_k_ftk_exp.hip:
-// T = T_k) and k_ftk_exp_times (tpl_k_ftk_exp_times.hip: T = t_i T_k, one workgroup per
-// time). Included only by those two units.
+// T = T_k), k_ftk_exp_times (tpl_k_ftk_exp_times.hip: T = t_i T_k, one workgroup per time)
+// and k_ftk_exp_times_batch (tpl_k_ftk_exp_times_batch.hip: one workgroup per time and
+// column of a batch group). Included only by those three units.
 #pragma once
 #include "tpl_klaunch.h"
 
@@ -351,6 +352,23 @@ __device__ __forceinline__ void ftk_exp_body(DevState S, int scale, Src src, Dst
   TPL_MARK(5);
   TPL_STAMP_TERMS(N);
 }
+// The source and destination of the kernels that evaluate exp at a list of times.
+// t T_k: every entry times t, one rounding (RN(t alpha_j), RN(t beta_j) — the arrays the host
+// built-in tpl_ftk_exp_t forms), before anything else uses it. The build's -ffp-contract=off
+// keeps the product out of the subtractions that follow (t alpha - c stays two roundings).
+struct ExpSrcTimes {
+  const double *al, *be;
+  double t;
+  __device__ __forceinline__ double alpha(int i) const { return t * al[i]; }
+  __device__ __forceinline__ double beta(int i) const { return t * be[i]; }
+};
+struct ExpDstTimes {  // a column of the coefficient table and its hand-back entry
+  double* y_;
+  int32_t* back;
+  __device__ __forceinline__ void y(int i, double v) const { y_[i] = v; }
+  __device__ __forceinline__ void hand_back() const { *back = 1; }
+  __device__ __forceinline__ void kept() const { *back = 0; }
+};
 // Dynamic LDS of a workgroup that runs ftk_exp_body on up to kcap rows.
 static inline size_t ftk_exp_lds_bytes(int kcap) { return (size_t)(4 * kcap + 4) * sizeof(double); }
 

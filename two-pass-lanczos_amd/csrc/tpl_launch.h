@@ -28,6 +28,13 @@ hipError_t ftk_exp(const DevState& S, int kcap, int scale, hipStream_t s);
 // zero column and back[i] = 1 where k_ftk_exp would hand the case back
 hipError_t ftk_exp_times(const DevState& S, int kcap, const double* ts, int m, double* Y, int ldy,
                          int32_t* back, int scale, hipStream_t s);
+// the same for every column of a batch group of nb (2 or 4) columns, one workgroup per
+// (time, column) (k_ftk_exp_times_batch, tpl_k_ftk_exp_times_batch.hip): column c's state is
+// its part of B (steps_c from its flags; B is only read), k <= B.kcap the steps asked for
+// (it sizes the LDS). Function i, column c goes to Y + (i nb + c) B.kcap — the layout
+// bp2_minit / bp2_xacc read — with back[c m + i] = 0, or zeros and back[c m + i] = 1
+hipError_t ftk_exp_times_batch(int nb, const BatchDev& B, int k, const double* ts, int m,
+                               double* Y, int32_t* back, int scale, hipStream_t s);
 hipError_t p2_init(int64_t n, const DevState& S, const double* b, double* v1, double* x,
                    double* Vcol, int dyn, hipStream_t s);
 // nflush: x terms the step applies (tpl::p2_flush: every third step and the last)

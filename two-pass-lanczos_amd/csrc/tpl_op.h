@@ -195,7 +195,12 @@ struct tpl_op_s {
   // until the first tpl_lanczos_two_pass_exp_times / tpl_op_ftk_exp_times_device call
   double* d_exp_ts = nullptr;
   int32_t *d_exp_back = nullptr, *h_exp_back = nullptr;
-  tpl::BatchBufs bat;               // lock-step batch solves (ensure_batch)
+  // the same for a batch group (ensure_exp_times_batch): the hand-back table of
+  // k_ftk_exp_times_batch, kBatchNbMax * TPL_MULTI_MAX int32 (entry c m + i), and its pinned
+  // host mirror; nullptr until the first tpl_lanczos_two_pass_batch_exp_times /
+  // tpl_op_ftk_exp_times_batch_device call. The times are d_exp_ts
+  int32_t *d_expb_back = nullptr, *h_expb_back = nullptr;
+  tpl::BatchBufs bat;              // lock-step batch solves (ensure_batch)
   std::map<std::pair<int, size_t>, tpl::GraphExec> graphs;
   // device allocations of this operator (pointer -> bytes): tpl_op_device_bytes
   std::map<const void*, size_t> allocs;
@@ -299,6 +304,12 @@ void ensure_multi(tpl_op_s* op, size_t m);
 // mirror of the second: allocated on the first such call, counted in device_bytes, freed
 // with the operator. No graph holds them.
 void ensure_exp_times(tpl_op_s* op);
+// The batch sibling's buffers: the times (op->d_exp_ts, shared with ensure_exp_times:
+// TPL_MULTI_MAX doubles, allocated by whichever comes first) and the hand-back table
+// (op->d_expb_back, kBatchNbMax * TPL_MULTI_MAX int32 = 1,024 bytes) with its pinned mirror.
+// Allocated on the first batch exp-times call, counted in device_bytes, freed with the
+// operator. No graph holds them.
+void ensure_exp_times_batch(tpl_op_s* op);
 // The interleaved work vectors, per-column state and hand-off buffers of a batch group of
 // nb (2 or 4) columns and k steps, allocated on demand and counted in device_bytes. They
 // grow with nb and k; growing drops the cached graphs. A layout rebuild frees them

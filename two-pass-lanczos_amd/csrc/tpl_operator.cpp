@@ -15,6 +15,7 @@ tpl_op_s::~tpl_op_s() {
   for (const auto& kv : allocs) hipFree(const_cast<void*>(kv.first));  // every dev_alloc
   if (st.h_state) hipHostFree(st.h_state);
   if (h_exp_back) hipHostFree(h_exp_back);
+  if (h_expb_back) hipHostFree(h_expb_back);
   if (ev0) hipEventDestroy(ev0);
   if (ev1) hipEventDestroy(ev1);
   for (hipEvent_t e : tev)
@@ -394,11 +395,25 @@ void ensure_multi(tpl_op_s* op, size_t m) {
   op->xcols = cols;
   op->ycap = cap;
 }
-void ensure_exp_times(tpl_op_s* op) {
-  if (!op->d_exp_ts) {
-    dev_alloc(op, &op->d_exp_ts, TPL_MULTI_MAX * sizeof(double));
-    HIPCHK(hipMemset(op->d_exp_ts, 0, TPL_MULTI_MAX * sizeof(double)));
+namespace {
+void ensure_exp_ts(tpl_op_s* op) {
+  if (op->d_exp_ts) return;
+  dev_alloc(op, &op->d_exp_ts, TPL_MULTI_MAX * sizeof(double));
+  HIPCHK(hipMemset(op->d_exp_ts, 0, TPL_MULTI_MAX * sizeof(double)));
+}
+} // namespace
+void ensure_exp_times_batch(tpl_op_s* op) {
+  constexpr size_t bytes = (size_t)kBatchNbMax * TPL_MULTI_MAX * sizeof(int32_t);
+  ensure_exp_ts(op);
+  if (!op->d_expb_back) {
+    dev_alloc(op, &op->d_expb_back, bytes);
+    HIPCHK(hipMemset(op->d_expb_back, 0, bytes));
   }
+  if (!op->h_expb_back)
+    HIPCHK(hipHostMalloc((void**)&op->h_expb_back, bytes, hipHostMallocDefault));
+}
+void ensure_exp_times(tpl_op_s* op) {
+  ensure_exp_ts(op);
   if (!op->d_exp_back) {
     dev_alloc(op, &op->d_exp_back, TPL_MULTI_MAX * sizeof(int32_t));
     HIPCHK(hipMemset(op->d_exp_back, 0, TPL_MULTI_MAX * sizeof(int32_t)));

@@ -472,6 +472,54 @@ void pass_two_multi(tpl_op_s* op, const double* b, const double* alphas, size_t 
   download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
   sync_checked(op);
 }
+// tpl_lanczos_two_pass_exp_times after its argument checks (on_device: m entries or NULL).
+void two_pass_exp_times(tpl_op_s* op, const double* b, size_t k, const double* ts, size_t m,
+                        double* x_out, int mem, int32_t* on_device) {
+  op->last_one_graph = false;
+  if (on_device) std::fill(on_device, on_device + m, 0);
+  ensure_state(op, k);
+  ensure_multi(op, m);
+  ensure_exp_times(op);
+  // 1. pass one, once; 2. straight behind it on the stream every exp(t_i T_k) e_1 at once
+  //    (steps_taken stays on the device), y_i = y'_i * ||b|| into the coefficient table
+  const bool dev = op->device_ftk != 0 && k <= kDevExpMaxK;
+  if (dev)
+    HIPCHK(hipMemcpyAsync(op->d_exp_ts, ts, m * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+  run_pass_one(op, b, k, mem, false, false);
+  if (dev) {
+    HIPCHK(launch::ftk_exp_times(op->st.S, (int)k, op->d_exp_ts, (int)m, op->d_Y, (int)op->ycap,
+                                 op->d_exp_back, 1, op->stream));
+    HIPCHK(hipMemcpyAsync(op->h_exp_back, op->d_exp_back, m * sizeof(int32_t),
+                          hipMemcpyDeviceToHost, op->stream));
+  }
+  const HostDecomp d = fetch_decomp(op);  // the call's one synchronisation before pass two
+  if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+  if (d.steps == 0) {
+    zero_out_cols(op, x_out, m, mem);
+    return;
+  }
+  // 3. the times handed back (without the device: all of them) on the host, in index
+  //    order; only their columns are uploaded
+  std::vector<double> Y, y;
+  double t = 0.0;
+  for (size_t i = 0; i < m; ++i) {
+    if (dev && !op->h_exp_back[i]) continue;
+    if (Y.empty()) Y.resize(m * d.steps);
+    t = ts[i];
+    call_ftk(&tpl_ftk_exp_t, &t, d, y);
+    double* col = Y.data() + i * d.steps;
+    for (size_t j = 0; j < d.steps; ++j) col[j] = y[j] * d.b_norm;
+    HIPCHK(hipMemcpyAsync(op->d_Y + i * op->ycap, col, d.steps * sizeof(double),
+                          hipMemcpyHostToDevice, op->stream));
+  }
+  // 4. one pass two for all of them
+  run_pass2_multi(op, d.steps, m);
+  download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+  sync_checked(op);
+  if (on_device)
+    for (size_t i = 0; i < m; ++i) on_device[i] = dev && !op->h_exp_back[i] ? 1 : 0;
+}
 } // namespace
 
 extern "C" {
@@ -544,50 +592,7 @@ tpl_status tpl_lanczos_two_pass_exp_times(tpl_op_t op, const double* b, int64_t 
       if (!std::isfinite(ts[i])) fail(TPL_ERR_INVALID_ARGUMENT, "every time t_i must be finite");
     const TimingOff untimed(op);
     const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS_MULTI);
-    op->last_one_graph = false;
-    if (on_device) std::fill(on_device, on_device + m, 0);
-    ensure_state(op, k);
-    ensure_multi(op, m);
-    ensure_exp_times(op);
-    // 1. pass one, once; 2. straight behind it on the stream every exp(t_i T_k) e_1 at once
-    //    (steps_taken stays on the device), y_i = y'_i * ||b|| into the coefficient table
-    const bool dev = op->device_ftk != 0 && k <= kDevExpMaxK;
-    if (dev)
-      HIPCHK(hipMemcpyAsync(op->d_exp_ts, ts, m * sizeof(double), hipMemcpyHostToDevice,
-                            op->stream));
-    run_pass_one(op, b, k, mem, false, false);
-    if (dev) {
-      HIPCHK(launch::ftk_exp_times(op->st.S, (int)k, op->d_exp_ts, (int)m, op->d_Y, (int)op->ycap,
-                                   op->d_exp_back, 1, op->stream));
-      HIPCHK(hipMemcpyAsync(op->h_exp_back, op->d_exp_back, m * sizeof(int32_t),
-                            hipMemcpyDeviceToHost, op->stream));
-    }
-    const HostDecomp d = fetch_decomp(op);  // the call's one synchronisation before pass two
-    if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
-    if (d.steps == 0) {
-      zero_out_cols(op, x_out, m, mem);
-      return;
-    }
-    // 3. the times handed back (without the device: all of them) on the host, in index
-    //    order; only their columns are uploaded
-    std::vector<double> Y, y;
-    double t = 0.0;
-    for (size_t i = 0; i < m; ++i) {
-      if (dev && !op->h_exp_back[i]) continue;
-      if (Y.empty()) Y.resize(m * d.steps);
-      t = ts[i];
-      call_ftk(&tpl_ftk_exp_t, &t, d, y);
-      double* col = Y.data() + i * d.steps;
-      for (size_t j = 0; j < d.steps; ++j) col[j] = y[j] * d.b_norm;
-      HIPCHK(hipMemcpyAsync(op->d_Y + i * op->ycap, col, d.steps * sizeof(double),
-                            hipMemcpyHostToDevice, op->stream));
-    }
-    // 4. one pass two for all of them
-    run_pass2_multi(op, d.steps, m);
-    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
-    sync_checked(op);
-    if (on_device)
-      for (size_t i = 0; i < m; ++i) on_device[i] = dev && !op->h_exp_back[i] ? 1 : 0;
+    two_pass_exp_times(op, b, k, ts, m, x_out, mem, on_device);
   });
 }
 
@@ -741,16 +746,24 @@ void download_group(tpl_op_s* op, double* X, int nb, int mem) {
     HIPCHK(hipMemcpyAsync(X, op->bat.d_stage, (size_t)n * nb * sizeof(double),
                           hipMemcpyDeviceToHost, op->stream));
 }
-// Pass one of a group; returns the decompositions' host mirror (synchronised).
-GroupHead pass_one_group(tpl_op_s* op, const double* B, size_t k, int nb, int mem) {
-  ensure_batch(op, nb, k);
+// Pass one of a group on the stream (ensure_batch first): the group's b, the lock-step steps.
+void enqueue_pass_one_group(tpl_op_s* op, const double* B, size_t k, int nb, int mem) {
   upload_group(op, B, nb, mem);
   run_pass1_batch(op, k, nb);
+}
+// The decompositions' host mirror of the group on the stream (synchronises).
+GroupHead fetch_group(tpl_op_s* op) {
   GroupHead g(op);
   HIPCHK(hipMemcpyAsync(g.h.data(), op->bat.d_state, g.decomp_bytes(), hipMemcpyDeviceToHost,
                         op->stream));
   sync_checked(op);
   return g;
+}
+// Pass one of a group; returns the decompositions' host mirror (synchronised).
+GroupHead pass_one_group(tpl_op_s* op, const double* B, size_t k, int nb, int mem) {
+  ensure_batch(op, nb, k);
+  enqueue_pass_one_group(op, B, k, nb, mem);
+  return fetch_group(op);
 }
 // tpl_lanczos_two_pass_batch after its argument checks.
 void two_pass_batch(tpl_op_s* op, const double* B, size_t s, size_t k, tpl_ftk_fn f, void* f_user,
@@ -1026,6 +1039,132 @@ tpl_status tpl_lanczos_pass_two_batch_multi(tpl_op_t op, const double* B, int64_
       sync_checked(op);
       c0 += (size_t)nb;
     }
+  });
+}
+
+tpl_status tpl_lanczos_two_pass_batch_exp_times(tpl_op_t op, const double* B, int64_t b_len,
+                                                size_t s, size_t k, const double* ts, size_t m,
+                                                double* x_out, int mem, int32_t* on_device) {
+  return guarded([&] {
+    check_batch_multi_args(op, B && ts && x_out, s, m);
+    check_b(op, B, b_len);
+    check_k(k);
+    for (size_t i = 0; i < m; ++i)
+      if (!std::isfinite(ts[i])) fail(TPL_ERR_INVALID_ARGUMENT, "every time t_i must be finite");
+    const TimingOff untimed(op);
+    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS_BATCH_MULTI);
+    op->last_one_graph = false;
+    if (on_device) std::fill(on_device, on_device + s * m, 0);
+    const bool dev = op->device_ftk != 0 && k <= kDevExpMaxK;
+    const size_t n = (size_t)op->part.n;
+    for (size_t c0 = 0; c0 < s;) {
+      const int nb = n == 0 ? 1 : group_width(s - c0);
+      if (nb == 1) {  // the single-b exp-times solve of that column
+        two_pass_exp_times(op, B + c0 * n, k, ts, m, x_out + c0 * m * n, mem,
+                           on_device ? on_device + c0 * m : nullptr);
+        ++c0;
+        continue;
+      }
+      ensure_batch(op, nb, k);
+      ensure_batch_multi(op, m, mem != TPL_MEM_DEVICE);
+      ensure_exp_times_batch(op);
+      BatchBufs& bb = op->bat;
+      // 1. pass one for the group's columns in lock-step; 2. straight behind it on the stream
+      //    every exp(t_i T_k) e_1 of every column at once (each steps_c stays on the device),
+      //    y_{c,i} = y'_{c,i} * ||b_c|| into the group's coefficient table
+      if (dev)
+        HIPCHK(hipMemcpyAsync(op->d_exp_ts, ts, m * sizeof(double), hipMemcpyHostToDevice,
+                              op->stream));
+      enqueue_pass_one_group(op, B + c0 * n, k, nb, mem);
+      if (dev) {
+        HIPCHK(launch::ftk_exp_times_batch(nb, bb.S, (int)k, op->d_exp_ts, (int)m, bb.d_my,
+                                           op->d_expb_back, 1, op->stream));
+        HIPCHK(hipMemcpyAsync(op->h_expb_back, op->d_expb_back, (size_t)nb * m * sizeof(int32_t),
+                              hipMemcpyDeviceToHost, op->stream));
+      }
+      GroupHead g = fetch_group(op);  // the group's one synchronisation before pass two
+      // 3. per column in order: the zero-vector check, then the times handed back (without
+      //    the device: all of them) on the host in index order; only their columns are
+      //    uploaded (host table: function i, column c at (i nb + c) k, alive until the sync)
+      std::vector<double> Yh, y;
+      size_t steps[kBatchNbMax];
+      double t = 0.0;
+      for (int c = 0; c < nb; ++c) {
+        const HostDecomp d = g.decomp((size_t)c);
+        if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+        steps[c] = d.steps;
+        for (size_t i = 0; i < m; ++i) {
+          const bool kept = dev && d.steps > 0 && !op->h_expb_back[(size_t)c * m + i];
+          if (on_device) on_device[(c0 + (size_t)c) * m + i] = kept ? 1 : 0;
+          if (kept) continue;
+          t = ts[i];
+          call_ftk(&tpl_ftk_exp_t, &t, d, y);
+          if (d.steps == 0) continue;
+          if (Yh.empty()) Yh.resize(m * (size_t)nb * k);
+          double* col = Yh.data() + (i * (size_t)nb + (size_t)c) * k;
+          for (size_t j = 0; j < d.steps; ++j) col[j] = y[j] * d.b_norm;
+          HIPCHK(hipMemcpyAsync(bb.d_my + (i * (size_t)nb + (size_t)c) * bb.kcap, col,
+                                d.steps * sizeof(double), hipMemcpyHostToDevice, op->stream));
+        }
+      }
+      // 4. one pass two for all nb x m results
+      run_pass2_batch_multi(op, steps, nb, m);
+      download_group_multi(op, x_out + c0 * m * n, nb, m, mem);
+      sync_checked(op);
+      c0 += (size_t)nb;
+    }
+  });
+}
+
+tpl_status tpl_op_ftk_exp_times_batch_device(tpl_op_t op, const double* alphas,
+                                             const double* betas, size_t ld, const size_t* steps,
+                                             size_t nb, const double* ts, size_t m, double* y_out,
+                                             int32_t* on_device) {
+  return guarded([&] {
+    if (!op || !alphas || !steps || !ts || !y_out || !on_device)
+      fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (nb != 2 && nb != 4) fail(TPL_ERR_INVALID_ARGUMENT, "nb must be 2 or 4");
+    if (m == 0 || m > (size_t)TPL_MULTI_MAX)
+      fail(TPL_ERR_INVALID_ARGUMENT, "m must be between 1 and TPL_MULTI_MAX");
+    size_t kmax = 0;
+    for (size_t c = 0; c < nb; ++c) {
+      if (steps[c] == 0 || steps[c] > ld)
+        fail(TPL_ERR_INVALID_ARGUMENT, "steps[c] must be between 1 and ld");
+      if (steps[c] > 1 && !betas) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+      kmax = std::max(kmax, steps[c]);
+    }
+    if (kmax > kDevExpMaxK) fail(TPL_ERR_UNSUPPORTED, "k above the device f(T_k) bound");
+    set_device(op);
+    if (op->dist) fail(TPL_ERR_UNSUPPORTED, "batch-multi solve of a partitioned operator");
+    ensure_batch(op, (int)nb, kmax);
+    ensure_batch_multi(op, m, false);
+    ensure_exp_times_batch(op);
+    BatchBufs& bb = op->bat;
+    // the group's state as pass one leaves it: steps_c, ||b_c|| = 1, no error
+    GroupHead g(op);
+    for (size_t c = 0; c < nb; ++c) {
+      g.flags(c)[2] = (int32_t)steps[c];
+      g.norms(c)[0] = 1.0;
+      std::memcpy(g.alphas(c), alphas + c * ld, steps[c] * sizeof(double));
+      if (steps[c] > 1) std::memcpy(g.betas(c), betas + c * ld, (steps[c] - 1) * sizeof(double));
+    }
+    HIPCHK(hipMemcpyAsync(bb.d_state, g.h.data(), g.decomp_bytes(), hipMemcpyHostToDevice,
+                          op->stream));
+    HIPCHK(hipMemcpyAsync(op->d_exp_ts, ts, m * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    HIPCHK(launch::ftk_exp_times_batch((int)nb, bb.S, (int)kmax, op->d_exp_ts, (int)m, bb.d_my,
+                                       op->d_expb_back, 0, op->stream));
+    // column (c m + i) of y_out <- function i, column c of the table: steps_c entries, zeros
+    // behind them
+    std::memset(y_out, 0, ld * nb * m * sizeof(double));
+    for (size_t c = 0; c < nb; ++c)
+      HIPCHK(hipMemcpy2DAsync(y_out + c * m * ld, ld * sizeof(double), bb.d_my + c * bb.kcap,
+                              nb * bb.kcap * sizeof(double), steps[c] * sizeof(double), m,
+                              hipMemcpyDeviceToHost, op->stream));
+    HIPCHK(hipMemcpyAsync(op->h_expb_back, op->d_expb_back, nb * m * sizeof(int32_t),
+                          hipMemcpyDeviceToHost, op->stream));
+    sync_checked(op);
+    for (size_t e = 0; e < nb * m; ++e) on_device[e] = op->h_expb_back[e] ? 0 : 1;
   });
 }
 

@@ -131,6 +131,9 @@ tpl_lanczos_two_pass_batch_multi = _sig("tpl_lanczos_two_pass_batch_multi", c_in
 tpl_lanczos_pass_two_batch_multi = _sig("tpl_lanczos_pass_two_batch_multi", c_int, c_void_p,
                                         c_void_p, c_int64, c_size_t, PD, PD, c_size_t,
                                         POINTER(c_size_t), PD, PD, c_size_t, c_void_p, c_int)
+tpl_lanczos_two_pass_batch_exp_times = _sig("tpl_lanczos_two_pass_batch_exp_times", c_int, c_void_p,
+                                            c_void_p, c_int64, c_size_t, c_size_t, PD, c_size_t,
+                                            c_void_p, c_int, POINTER(c_int32))
 tpl_load_kkt_system = _sig("tpl_load_kkt_system", c_int, c_char_p, c_char_p, POINTER(CsrHost))
 tpl_csr_host_free = _sig("tpl_csr_host_free", None, POINTER(CsrHost))
 tpl_generate_kkt = _sig("tpl_generate_kkt", c_int, c_int64, c_int64, ctypes.c_uint64,
@@ -166,6 +169,9 @@ tpl_op_ftk_device = _sig("tpl_op_ftk_device", c_int, c_void_p, c_int, PD, c_size
                          POINTER(c_int))
 tpl_op_ftk_exp_times_device = _sig("tpl_op_ftk_exp_times_device", c_int, c_void_p, PD, c_size_t,
                                    PD, PD, c_size_t, PD, POINTER(c_int32))
+tpl_op_ftk_exp_times_batch_device = _sig("tpl_op_ftk_exp_times_batch_device", c_int, c_void_p, PD,
+                                         PD, c_size_t, POINTER(c_size_t), c_size_t, PD, c_size_t,
+                                         PD, POINTER(c_int32))
 tpl_op_set_order_groups = _sig("tpl_op_set_order_groups", c_int, c_void_p, c_int32)
 tpl_op_order_groups = _sig("tpl_op_order_groups", c_int32, c_void_p)
 
@@ -274,3 +280,4 @@ tpl_fused_pass_two_rows = _sig("tpl_fused_pass_two_rows", c_int, c_int64, c_void
                                ctypes.POINTER(c_int64))
 EXPORTED += ["tpl_op_set_fused_pass_two", "tpl_fused_pass_two_rows"]
 EXPORTED += ["tpl_ftk_exp_t", "tpl_lanczos_two_pass_exp_times", "tpl_op_ftk_exp_times_device"]
+EXPORTED += ["tpl_lanczos_two_pass_batch_exp_times", "tpl_op_ftk_exp_times_batch_device"]

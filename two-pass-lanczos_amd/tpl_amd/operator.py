@@ -346,6 +346,39 @@ class HipCsrOp:
             on.ctypes.data_as(POINTER(ctypes.c_int32))))
         return y[:m].T, on[:m].astype(bool)
 
+    def ftk_exp_times_batch_device(self, alphas_list, betas_list, ts, ld=None):
+        """The device kernel of ``lanczos_two_pass_batch_exp_times`` alone, on a group of nb
+        (2 or 4) tridiagonals: ``alphas_list[c]`` (steps_c entries) and ``betas_list[c]``
+        (steps_c - 1) are column c, ``ld`` the columns' stride (default: the largest steps_c).
+        -> (Y of shape (ld, m, nb), strides (1, ld, ld m): ``Y[:, i, c]`` holds the steps_c
+        unscaled entries of exp(t_i T_c) e_1 and zeros behind them; (m, nb) bool array:
+        evaluated on the device? — a handed-back column is zero)."""
+        als = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in alphas_list]
+        bes = [np.ascontiguousarray(b, dtype=np.float64).reshape(-1) for b in betas_list]
+        if len(als) != len(bes):
+            raise ValueError("one betas array per alphas array")
+        t = np.ascontiguousarray(np.atleast_1d(np.asarray(ts, dtype=np.float64)).reshape(-1))
+        nb, m = len(als), t.shape[0]
+        st = [a.shape[0] for a in als]
+        for c in range(nb):
+            if bes[c].shape[0] < st[c] - 1:
+                raise ValueError("betas_list[c] must hold steps_c - 1 entries")
+        ld = max(st + [1]) if ld is None else int(ld)
+        w = max(ld, 1)
+        al, be = np.zeros((max(nb, 1), w)), np.zeros((max(nb, 1), w))
+        for c in range(nb):
+            nc = min(st[c], w)  # a steps_c above ld is the library's to refuse
+            al[c, :nc] = als[c][:nc]
+            be[c, :max(nc - 1, 0)] = bes[c][:max(nc - 1, 0)]
+        steps = (ctypes.c_size_t * max(nb, 1))(*st)
+        y = np.zeros((max(nb, 1), max(m, 1), w))
+        on = np.zeros(max(nb * m, 1), dtype=np.int32)
+        pd = lambda v: v.ctypes.data_as(POINTER(c_double))
+        check(_lib.tpl_op_ftk_exp_times_batch_device(
+            self._op, pd(al), pd(be), ld, steps, nb, pd(t), m, pd(y),
+            on.ctypes.data_as(POINTER(ctypes.c_int32))))
+        return y[:, :m].transpose(2, 1, 0), on[:nb * m].reshape(nb, m).T.astype(bool)
+
     def enable_timing(self, on: bool = True):
         """Record HIP events inside the captured passes of later solves."""
         check(_lib.tpl_op_enable_timing(self._op, 1 if on else 0))

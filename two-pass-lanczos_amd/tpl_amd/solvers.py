@@ -30,6 +30,10 @@ with ``f_tk_solvers[i]`` evaluated on the host.
 the matrix exponential at a list of times: exp(t_i A) b for every t_i over one Krylov space,
 every exp(t_i T_k) e_1 evaluated at once on the device between the two shared passes. It
 returns shape (n, m) with strides (1, n).
+
+``lanczos_two_pass_batch_exp_times(operator, B, k, ts)`` (no reference counterpart) is the same
+for the s columns of ``B`` in lock-step: exp(t_i A) b_c, every exp(t_i T_k) e_1 of a group of
+columns evaluated by one device launch. It returns shape (n, m, s) with strides (1, n, n m).
 """
 from __future__ import annotations
 
@@ -160,3 +164,27 @@ def lanczos_two_pass_batch_multi(operator, B, k: int, f_tk_solvers):
                 raise ftk.remap_error(e, keep) from None
         raise
     return x.permute(2, 1, 0) if hasattr(x, "permute") else x.transpose(2, 1, 0)
+
+
+def lanczos_two_pass_batch_exp_times(operator, B, k: int, ts, return_on_device: bool = False):
+    """exp(t_i A) b_c for the m times ``ts`` and every column c of ``B`` (n x s) by ONE run:
+    per group of columns pass one in lock-step, every exp(t_i T_k) e_1 of every column at once
+    on the device (one workgroup per time and column; what the device hands back, and with
+    ``set_device_ftk(0)`` everything, runs the native host ``exp_t``), one pass two for the
+    group's results. Returns shape (n, m, s): ``X[:, i, c]`` is bitwise
+    ``lanczos_two_pass_exp_times(operator, B[:, c], k, ts)[:, i]``. With ``return_on_device``
+    also the (m, s) bool array of the (time, column) pairs whose y the device computed."""
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(ts, dtype=np.float64)).reshape(-1))
+    m = int(t.shape[0])
+    if m == 0:
+        raise ValueError("ts must hold at least one time")
+    bv = Cols(B)
+    bv.check_rows(operator)
+    operator = as_operator(operator)
+    x = bv.empty(bv.s, m, bv.n)  # C-order (s, m, n) == column-major n x (s m), column c m + i
+    on = np.zeros(bv.s * m, dtype=np.int32)
+    check(_lib.tpl_lanczos_two_pass_batch_exp_times(
+        operator.handle, bv.ptr, bv.n, bv.s, k, t.ctypes.data_as(_lib.PD), m, Vec.ptr_of(x),
+        bv.mem, on.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    X = x.permute(2, 1, 0) if hasattr(x, "permute") else x.transpose(2, 1, 0)
+    return (X, on.reshape(bv.s, m).T.astype(bool)) if return_on_device else X
