@@ -12,11 +12,11 @@
 // they reference — the hub set H, at most kFusedHubMax rows — step together in one workgroup.
 //   k_p2_hub   one thread per long row: v_j[r] replaces the sum in the cache row of step j;
 //              one more workgroup owns H (its rows' only reader and writer in the cache) and
-//              exchanges v_j through LDS, one barrier per step.
-//   k_p2_rows  one workgroup per short chunk: a thread keeps its rows' entries, v and x in
-//              registers; per step the workgroup stages the long rows' v_j from the cache row
-//              into LDS (double-buffered: step j + 1's loads are issued before step j's
-//              arithmetic) and the rows gather from there.
+//              exchanges v_j inside one wave (|H| <= 64) or through LDS, one barrier per step.
+//   k_p2_rows  one workgroup per four short chunks: a thread keeps its rows' entries, v and
+//              x in registers; per step the workgroup stages the long rows' v_j from the
+//              cache row into LDS once for its chunks (double-buffered, the loads two steps
+//              ahead in registers) and the rows gather from there.
 // No workgroup waits on another: the only dependency between workgroups is the kernel
 // boundary between the two launches.
 //
@@ -55,7 +55,7 @@ struct FusedP2Args {
   const int32_t* s_cbase;
   const int32_t* c_base;
   const int32_t* c_width;
-  int32_t n_short, s_width, val_i8, s_col16;
+  int32_t n_short, n_chunks, s_width, val_i8, s_col16;
 };
 
 __device__ __forceinline__ int fused_steps(const FusedP2Args& a) {
@@ -65,15 +65,120 @@ __device__ __forceinline__ int fused_steps(const FusedP2Args& a) {
 
 // One step of one row (EpiPass2R::apply): s = (A v_j)_i, cv = the step's record, lane-wise
 // (lane l of the wave holds field l & 7). vp is 0.0 at j = 1, where the record's beta is 0.
-__device__ __forceinline__ void fused_step(double s, double cv, double& vc, double& vp, double& xv) {
-  const double beta_sub = readlane_f64(cv, 0), alpha = readlane_f64(cv, 1);
-  const double invb = readlane_f64(cv, 2), ycoef = readlane_f64(cv, 3);
-  double w = s - beta_sub * vp;
-  w = w - alpha * vc;
-  const double vn = w * invb;
-  xv = xv + ycoef * vn;
+struct StepRec {
+  double beta_sub, alpha, invb, ycoef;
+};
+__device__ __forceinline__ StepRec rec_fields(double cv) {
+  return {readlane_f64(cv, 0), readlane_f64(cv, 1), readlane_f64(cv, 2), readlane_f64(cv, 3)};
+}
+__device__ __forceinline__ void fused_step_r(double s, const StepRec& r, double& vc, double& vp,
+                                             double& xv) {
+  double w = s - r.beta_sub * vp;
+  w = w - r.alpha * vc;
+  const double vn = w * r.invb;
+  xv = xv + r.ycoef * vn;
   vp = vc;
   vc = vn;
+}
+__device__ __forceinline__ void fused_step(double s, double cv, double& vc, double& vp, double& xv) {
+  fused_step_r(s, rec_fields(cv), vc, vp, xv);
+}
+
+// k_p2_hub's store of v_j[r] into a cache row, as a raw buffer store over exactly that row
+// (base `row`, n_long * 8 bytes): a lane that must not write passes kLaneOff, which the
+// hardware's range check of the descriptor drops. The store is then one instruction on
+// every path — no branch around it — so the compiler counts it exactly in the s_waitcnt
+// vmcnt of the prefetch loads behind it (a store under `if` made it assume none was issued
+// and wait for loads several steps younger than the one it needed).
+constexpr uint32_t kLaneOff = 0x80000000u;  // past any row: n_long * 8 <= 16 KiB
+__device__ __forceinline__ void st_cache_row(double* row, int nl, uint32_t off, double v) {
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  // word 3: an untyped 32-bit element, no swizzle; stride 0: `off` is a byte offset
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(row, 0, nl * 8, 0x00020000);
+  u32x2 d;
+  d.x = (uint32_t)__double2loint(v);
+  d.y = (uint32_t)__double2hiint(v);
+  __builtin_amdgcn_raw_buffer_store_b64(d, r, off, 0, 0);
+}
+
+// The chain of one thread of k_p2_hub over steps 1 .. last. MODE: a long-row workgroup; the
+// hub workgroup exchanging v_j through LDS, one barrier per step; or, where H fits one wave
+// (|H| <= 64: the KKT instances have 3), the hub workgroup's first wave alone, its open rows
+// reading the other lanes' v_j by a wave shuffle — no LDS round trip and no barrier on what
+// is the kernel's longest chain. The sums and records run kHubAhead
+// steps ahead of the chain in yb / cb: they do not depend on it. The main loop takes whole
+// blocks of kHubAhead steps with no exit inside a block, each step refilling its own slot
+// (one cache load, one record load), so no wait in a block asks for a load of that block; the
+// last `last mod kHubAhead` steps run from the registers and load nothing.
+enum HubMode { kHubLong, kHubLds, kHubWave };
+constexpr int kWave = 64;
+template <HubMode MODE>
+__device__ __forceinline__ void hub_chain(const FusedP2Args& a, double (*vh)[kTPB], int last,
+                                          int lc, bool writes, bool open,
+                                          const int (&ent)[kFusedWidth],
+                                          const double (&av)[kFusedWidth], double& vc, double& vp,
+                                          double& xv) {
+  const int t = threadIdx.x;
+  const int nl = a.n_long;
+  double yb[kHubAhead], cb[kHubAhead];
+#pragma unroll
+  for (int u = 0; u < kHubAhead; ++u) {
+    const int jj = clampi(1 + u, last);
+    yb[u] = a.ycache[(size_t)(jj - 1) * nl + lc];
+    cb[u] = a.rec[8 * (size_t)jj + (t & 7)];
+  }
+  const uint32_t soff = writes ? (uint32_t)lc * 8u : kLaneOff;
+  auto step = [&](int j, double s, double cv) {
+    st_cache_row(a.ycache + (size_t)(j - 1) * nl, nl, soff, vc);  // v_j[r] in the sum's place
+    if (MODE == kHubLds) {
+      double* vb = vh[j & 1];
+      vb[t] = vc;
+      __syncthreads();
+      if (open) {  // short_chunk_w's sum over the row's entries
+        s = 0.0;
+#pragma unroll
+        for (int k = 0; k < kFusedWidth; ++k) {
+          const double prod = av[k] * vb[ent[k] < 0 ? 0 : ent[k]];
+          s = s + (ent[k] >= 0 ? prod : -0.0);
+        }
+      }
+    }
+    if (MODE == kHubWave) {  // the same sum; every lane takes part in the shuffles
+      double so = 0.0;
+#pragma unroll
+      for (int k = 0; k < kFusedWidth; ++k) {
+        const double prod = av[k] * __shfl(vc, ent[k] < 0 ? 0 : ent[k], kWave);
+        so = so + (ent[k] >= 0 ? prod : -0.0);
+      }
+      s = open ? so : s;
+    }
+    fused_step(s, cv, vc, vp, xv);
+  };
+  const int nblk = last / kHubAhead;
+  int j0 = 1;
+  // every load so far has landed before the first block (s_waitcnt vmcnt(0); step 1 waits
+  // for its own anyway): the compiler folds the loop's entry state into the waits of every
+  // iteration, and with these loads pending it asked each block for the previous block's last
+  if (nblk > 0) __builtin_amdgcn_s_waitcnt(0x0F70);
+  for (int b = 0; b < nblk; ++b, j0 += kHubAhead) {
+#pragma unroll
+    for (int u = 0; u < kHubAhead; ++u) {
+      const int j = j0 + u;
+      step(j, yb[u], cb[u]);
+      // the slot's refill comes after its last use and stays there: a load hoisted over the
+      // use needs a second register and a copy at the loop's end, which waits for the load
+      __builtin_amdgcn_sched_barrier(0);
+      const int jn = clampi(j + kHubAhead, last);
+      yb[u] = a.ycache[(size_t)(jn - 1) * nl + lc];
+      cb[u] = a.rec[8 * (size_t)jn + (t & 7)];
+    }
+  }
+  const int rem = last - nblk * kHubAhead;  // uniform
+#pragma unroll
+  for (int u = 0; u < kHubAhead - 1; ++u) {
+    if (u >= rem) break;
+    step(j0 + u, yb[u], cb[u]);
+  }
 }
 
 // Grid: [ceil(n_long / 256) long-row workgroups][the hub workgroup, if n_hub > 0].
@@ -119,40 +224,13 @@ __global__ __launch_bounds__(kTPB) void k_p2_hub(FusedP2Args a) {
     for (int h = a.n_open; h < a.n_hub; ++h) live = live && a.h_row[h] != (int32_t)row;
   }
   double vc = a.v1[row], vp = 0.0, xv = a.x[row];
-  // the sums and records of the next kHubAhead steps: they do not depend on the chain
-  double yb[kHubAhead], cb[kHubAhead];
-#pragma unroll
-  for (int u = 0; u < kHubAhead; ++u) {
-    const int jj = clampi(1 + u, last);
-    yb[u] = a.ycache[(size_t)(jj - 1) * nl + lc];
-    cb[u] = a.rec[8 * (size_t)jj + (t & 7)];
-  }
-  for (int j0 = 1; j0 <= last; j0 += kHubAhead) {
-#pragma unroll
-    for (int u = 0; u < kHubAhead; ++u) {
-      const int j = j0 + u;
-      double s = yb[u];
-      const double cv = cb[u];
-      const int jn = clampi(j + kHubAhead, last);
-      yb[u] = a.ycache[(size_t)(jn - 1) * nl + lc];
-      cb[u] = a.rec[8 * (size_t)jn + (t & 7)];
-      if (j > last) break;  // uniform
-      if (live && !open) a.ycache[(size_t)(j - 1) * nl + lc] = vc;  // v_j[r] in the sum's place
-      if (hub) {
-        double* vb = vh[j & 1];
-        vb[t] = vc;
-        __syncthreads();
-        if (open) {  // short_chunk_w's sum over the row's entries
-          s = 0.0;
-#pragma unroll
-          for (int k = 0; k < kFusedWidth; ++k) {
-            const double prod = av[k] * vb[ent[k] < 0 ? 0 : ent[k]];
-            s = s + (ent[k] >= 0 ? prod : -0.0);
-          }
-        }
-      }
-      fused_step(s, cv, vc, vp, xv);
-    }
+  if (hub && a.n_hub <= kWave) {
+    if (t >= kWave) return;  // whole waves without a row of H, and no barrier ahead of them
+    hub_chain<kHubWave>(a, vh, last, lc, live && !open, open, ent, av, vc, vp, xv);
+  } else if (hub) {
+    hub_chain<kHubLds>(a, vh, last, lc, live && !open, open, ent, av, vc, vp, xv);
+  } else {
+    hub_chain<kHubLong>(a, vh, last, lc, live, false, ent, av, vc, vp, xv);
   }
   if (live) st_out(a.x + row, xv);
 }
@@ -171,16 +249,32 @@ __device__ __forceinline__ double fused_val(const FusedP2Args& a, int e) {
   return reinterpret_cast<const double*>(a.s_val)[e];
 }
 
-// Grid: one workgroup per short chunk. W: the widest chunk (1 .. kFusedWidth); NL: cache-row
-// loads per thread, ceil(n_long / 256). Dynamic LDS: 2 n_long doubles.
+// k_p2_rows: kRowsGroup consecutive chunks per workgroup (256 threads each, staging the cache
+// row once for all of them), and the cache row and record of the next kRowsDepth steps in
+// registers. Fixed choices of the measurements in DESIGN.md 6.1 / 6.3: with four chunks a
+// thread stages at most two words per step (n_long <= 2,048), so one depth serves every
+// instance, within 128 VGPRs.
+constexpr int kRowsGroup = 4;
+constexpr int kRowsThreads = kTPB * kRowsGroup;
+constexpr int kRowsDepth = 2;
+
+// Grid: one workgroup per kRowsGroup short chunks. W: the widest chunk (1 .. kFusedWidth);
+// NL: ceil(n_long / 256), so ceil(NL / kRowsGroup) cache-row loads per thread. Dynamic LDS:
+// 2 n_long doubles. The waves of a chunk past the last one take every barrier and stage with
+// the rest; their rows are masked as open rows are.
 template <int W, int NL>
-__global__ __launch_bounds__(kTPB) void k_p2_rows(FusedP2Args a) {
+__global__ __launch_bounds__(kRowsThreads) void k_p2_rows(FusedP2Args a) {
   extern __shared__ double lds[];
+  constexpr int NLC = (NL + kRowsGroup - 1) / kRowsGroup;
+  constexpr int D = kRowsDepth;
   const int steps = fused_steps(a);
   if (steps < 2) return;  // uniform over the grid
   const int last = steps - 1;
-  const int t = threadIdx.x;
-  const int chunk = blockIdx.x;
+  const int tw = threadIdx.x;  // the staging index
+  const int t = tw % kTPB;     // the thread of its chunk
+  const int chunk_w = blockIdx.x * kRowsGroup + tw / kTPB;
+  const bool have = chunk_w < a.n_chunks;
+  const int chunk = have ? chunk_w : a.n_chunks - 1;
   const int nl = a.n_long;
   const int first_long = (int)(a.n - nl);
   // the chunk's entries: width, base and order as short_chunk has them
@@ -196,7 +290,7 @@ __global__ __launch_bounds__(kTPB) void k_p2_rows(FusedP2Args a) {
 #pragma unroll
   for (int q = 0; q < kRowsPerThread; ++q) {
     const int p = chunk * kChunkRows + q * kTPB + t;
-    live[q] = p < a.n_short;
+    live[q] = have && p < a.n_short;
     row[q] = clampi(p, a.n_short - 1);  // the long rows are last: position = row
 #pragma unroll
     for (int k = 0; k < W; ++k) {
@@ -220,23 +314,34 @@ __global__ __launch_bounds__(kTPB) void k_p2_rows(FusedP2Args a) {
     vp[q] = 0.0;
     xv[q] = a.x[row[q]];
   }
-  // step 1's cache row and record
-  double st[NL], cvn;
+  // slot d: the cache row (this thread's NLC words of it) and the record of step 1 + d, then
+  // of every D-th step after it
+  double st[D][NLC], cvr[D];
 #pragma unroll
-  for (int u = 0; u < NL; ++u) st[u] = a.ycache[clampi(t + u * kTPB, nl - 1)];
-  cvn = a.rec[8 + (t & 7)];
-  for (int j = 1; j <= last; ++j) {
+  for (int d = 0; d < D; ++d) {
+    const int jj = clampi(1 + d, last);
+#pragma unroll
+    for (int u = 0; u < NLC; ++u)
+      st[d][u] = a.ycache[(size_t)(jj - 1) * nl + clampi(tw + u * kRowsThreads, nl - 1)];
+    cvr[d] = a.rec[8 * (size_t)jj + (tw & 7)];
+  }
+  // one step from slot d. The slot's last uses (the LDS writes, the record's fields) come
+  // before its refill, which is then in flight over this and the next D - 1 steps' barriers,
+  // gathers and arithmetic
+  auto step = [&](int j, int d, auto refill) {
     double* vb = lds + (j & 1) * nl;
 #pragma unroll
-    for (int u = 0; u < NL; ++u)
-      if (t + u * kTPB < nl) vb[t + u * kTPB] = st[u];
-    const double cv = cvn;
-    // step j + 1's loads, in flight over this step's barrier, gathers and arithmetic
-    const int jn = clampi(j + 1, last);
+    for (int u = 0; u < NLC; ++u)  // all but the last load lie wholly inside the row
+      if (u < NLC - 1 || tw + u * kRowsThreads < nl) vb[tw + u * kRowsThreads] = st[d][u];
+    const StepRec r = rec_fields(cvr[d]);
+    if (decltype(refill)::value) {
+      __builtin_amdgcn_sched_barrier(0);
+      const int jn = clampi(j + D, last);
 #pragma unroll
-    for (int u = 0; u < NL; ++u)
-      st[u] = a.ycache[(size_t)(jn - 1) * nl + clampi(t + u * kTPB, nl - 1)];
-    cvn = a.rec[8 * (size_t)jn + (t & 7)];
+      for (int u = 0; u < NLC; ++u)
+        st[d][u] = a.ycache[(size_t)(jn - 1) * nl + clampi(tw + u * kRowsThreads, nl - 1)];
+      cvr[d] = a.rec[8 * (size_t)jn + (tw & 7)];
+    }
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < kRowsPerThread; ++q) {
@@ -247,8 +352,22 @@ __global__ __launch_bounds__(kTPB) void k_p2_rows(FusedP2Args a) {
         const double prod = av[q][k] * (li[q][k] == -2 ? vc[q] : g);
         s = s + (li[q][k] != -1 ? prod : -0.0);  // padding adds -0.0: exact
       }
-      fused_step(s, cv, vc[q], vp[q], xv[q]);
+      fused_step_r(s, r, vc[q], vp[q], xv[q]);
     }
+  };
+  // whole blocks of D steps without an exit, then the last `last mod D` from the registers
+  const int nblk = last / D;
+  int j0 = 1;
+  if (nblk > 0) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), as in hub_chain
+  for (int b = 0; b < nblk; ++b, j0 += D) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) step(j0 + d, d, std::true_type{});
+  }
+  const int rem = last - nblk * D;  // uniform
+#pragma unroll
+  for (int d = 0; d < D - 1; ++d) {
+    if (d >= rem) break;
+    step(j0 + d, d, std::false_type{});
   }
 #pragma unroll
   for (int q = 0; q < kRowsPerThread; ++q)
@@ -274,6 +393,7 @@ static FusedP2Args fused_args(const CsrDev& A, const DevState& S, const double* 
   a.c_base = A.c_base;
   a.c_width = A.c_width;
   a.n_short = A.n_short;
+  a.n_chunks = A.n_chunks;
   a.s_width = A.s_width;
   a.val_i8 = A.val_i8;
   a.s_col16 = A.s_col16;
@@ -300,7 +420,8 @@ static bool rows_nl(int nloads, const FusedP2Args& a, int grid, size_t lds, hipS
                     std::integer_sequence<int, NLs...>) {
   auto one = [&](auto NL) {
     if (nloads != decltype(NL)::value + 1) return false;
-    hipLaunchKernelGGL((k_p2_rows<W, decltype(NL)::value + 1>), dim3(grid), dim3(kTPB), lds, s, a);
+    hipLaunchKernelGGL((k_p2_rows<W, decltype(NL)::value + 1>), dim3(grid), dim3(kRowsThreads),
+                       lds, s, a);
     return true;
   };
   return (one(std::integral_constant<int, NLs>{}) || ...);
@@ -318,12 +439,13 @@ hipError_t p2_fused_rows(const CsrDev& A, const DevState& S, const double* ycach
   // W: the widest chunk. A uniform layout has its width; per-chunk widths (s_width == 0)
   // run the widest instance, each chunk masking the entries past its own width
   const int w = A.s_width > 0 ? A.s_width : kFusedWidth;
+  const int grid = (A.n_chunks + kRowsGroup - 1) / kRowsGroup;
   bool ok = false;
   switch (w) {
-    case 1: ok = rows_nl<1>(nloads, a, A.n_chunks, lds, s, nls); break;
-    case 2: ok = rows_nl<2>(nloads, a, A.n_chunks, lds, s, nls); break;
-    case 3: ok = rows_nl<3>(nloads, a, A.n_chunks, lds, s, nls); break;
-    case 4: ok = rows_nl<4>(nloads, a, A.n_chunks, lds, s, nls); break;
+    case 1: ok = rows_nl<1>(nloads, a, grid, lds, s, nls); break;
+    case 2: ok = rows_nl<2>(nloads, a, grid, lds, s, nls); break;
+    case 3: ok = rows_nl<3>(nloads, a, grid, lds, s, nls); break;
+    case 4: ok = rows_nl<4>(nloads, a, grid, lds, s, nls); break;
     default: break;
   }
   return ok ? hipGetLastError() : hipErrorInvalidConfiguration;
