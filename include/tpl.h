@@ -197,6 +197,18 @@ int tpl_ftk_exp(const double* alphas, size_t n_alphas, const double* betas, size
 int tpl_ftk_sq(const double* alphas, size_t n_alphas, const double* betas, size_t n_betas,
                double* y_out, size_t y_cap, size_t* y_len, char* err_msg, size_t err_cap,
                void* user);
+/* The residual history of the inverse solve: res_out[m - 1], m = 1 .. L = min(n_alphas,
+ * n_betas), is the relative Lanczos residual ||b - A x_m|| / ||b|| = beta_m |e_m^T T_m^{-1}
+ * e_1| of the m-step iterate x_m = ||b|| V_m T_m^{-1} e_1, from tpl_ftk_inv's own
+ * elimination: with the running row {d, b} after rows 0 .. m - 2 are eliminated,
+ * res[m - 1] = fabs(betas[m - 1] * (b / d)) — an IEEE divide, a multiply, fabs, no
+ * contraction. A zero pivot gives inf or NaN (neither is ever <= a finite tolerance). The
+ * estimate follows the true residual down to about 1e-14 relative and keeps falling where
+ * the true one stalls at rounding level; on a singular matrix it does not fall at all.
+ * *res_len (may be NULL) receives L; non-zero return: res_cap < L or a NULL array with
+ * L > 0. A k-step pass one has k - 1 betas, so its history has k - 1 entries.         */
+int tpl_ftk_inv_residuals(const double* alphas, size_t n_alphas, const double* betas,
+                          size_t n_betas, double* res_out, size_t res_cap, size_t* res_len);
 /* exp_t: y' = exp(t T_k) e_1 — exp(tA) b at time t. `user` points to one double, t; NULL:
  * non-zero return with a message. tpl_ftk_exp on the arrays t * alphas, t * betas (every
  * entry times t, rounded once), so bitwise what a caller gets who scales T_k and calls
@@ -221,6 +233,33 @@ tpl_status tpl_lanczos(tpl_op_t op, const double* b, int64_t b_len, size_t k,
  * On an error x_out is unspecified.                                               */
 tpl_status tpl_lanczos_two_pass(tpl_op_t op, const double* b, int64_t b_len, size_t k,
                                 tpl_ftk_fn f, void* f_user, double* x_out, int mem);
+/* x = A^{-1} b by the two-pass solve with the built-in inv, stopped at a residual tolerance
+ * (an extension: the reference's solvers take a fixed k). With `steps_taken` steps of a
+ * kmax-step pass one (fewer than kmax after a breakdown) and res = tpl_ftk_inv_residuals of
+ * its decomposition: m* = the smallest m in 1 .. steps_taken - 1 with res[m - 1] <= tol and
+ * *converged = 1, or m* = steps_taken and *converged = 0 if there is none. x_out is bitwise
+ * tpl_lanczos_two_pass(op, b, m*, tpl_ftk_inv); *steps = m*. res_out (capacity kmax, or
+ * NULL) receives the history up to the last entry that was formed, *res_len entries: the
+ * first min(m*, steps_taken - 1) are always there and bitwise tpl_ftk_inv_residuals';
+ * how many follow them is unspecified (*res_len is 0 when res_out is NULL). steps,
+ * converged and res_len may be NULL.
+ * Where tpl_lanczos_two_pass would run inv on the device for k = kmax
+ * (tpl_op_set_device_ftk: a single GPU, mode 2 up to kmax = 500, mode 1 up to 1365) the
+ * call is ONE graph, cached per kmax and replayed for any tol: pass one's elimination
+ * workgroup forms each residual as its row is done and raises the stop on the device, about
+ * two steps run past m*, every later launch of pass one returns at once, and pass two takes
+ * m* from the device. tpl_op_flags bit 5 reads 1 afterwards, bits 8 and 9 as after
+ * tpl_lanczos_two_pass with k = kmax; the long-row cache follows TPL_LONG_CACHE_TWO_PASS.
+ * Everywhere else (mode 0, a larger kmax, a partitioned operator) the call is composed on
+ * the host — tpl_lanczos_pass_one to kmax, the history and the rule, tpl_ftk_inv on the
+ * first m* rows, tpl_lanczos_pass_two — with the same results, bit for bit.
+ * Errors: NULL op or x_out, then tol NaN or negative: TPL_ERR_INVALID_ARGUMENT before any
+ * device work (tol = +inf is valid: m* = 1 when kmax >= 2); every other error is
+ * tpl_lanczos_two_pass's (a host-only plan, b's length, kmax = 0, a zero b). No live timing:
+ * tpl_op_pass_timing keeps its values.                                                  */
+tpl_status tpl_lanczos_two_pass_inv_tol(tpl_op_t op, const double* b, int64_t b_len, size_t kmax,
+                                        double tol, double* x_out, int mem, size_t* steps,
+                                        int32_t* converged, double* res_out, size_t* res_len);
 /* ---- f_1(A) b ... f_m(A) b over one Krylov space (an extension: the reference's
  *      f_tk_solver returns a Mat and rejects ncols != 1, src/solvers.rs:78,158) ------
  * Pass one and the basis pass two regenerates depend on (A, b, k) only; the functions

@@ -392,6 +392,18 @@ inline FtkSolver inv() { return Builtin{tpl_ftk_inv}; }  // T_k^{-1} e_1 (tridia
 // include/tpl.h tpl_op_set_device_ftk) — tpl_op_set_device_ftk(op, 0) forces the host QL
 inline FtkSolver exp() { return Builtin{tpl_ftk_exp}; }
 inline FtkSolver sq() { return Builtin{tpl_ftk_sq}; }    // T_k^2 e_1
+// The residual history of the inverse solve (tpl_ftk_inv_residuals): entry m - 1 is the
+// relative Lanczos residual of the m-step iterate, m = 1 .. min(alphas.size(), betas.size()).
+inline std::vector<double> inv_residuals(const std::vector<double>& alphas,
+                                         const std::vector<double>& betas) {
+  std::vector<double> res(std::min(alphas.size(), betas.size()));
+  size_t len = 0;
+  if (tpl_ftk_inv_residuals(alphas.data(), alphas.size(), betas.data(), betas.size(), res.data(),
+                            res.size(), &len))
+    throw std::runtime_error("tpl_ftk_inv_residuals failed");
+  res.resize(len);
+  return res;
+}
 }  // namespace ftk
 
 namespace detail {
@@ -514,6 +526,31 @@ inline Mat lanczos_two_pass_exp_times(const HipCsrOp& op, const std::vector<doub
   detail::check(tpl_lanczos_two_pass_exp_times(op.handle(), b.data(), (int64_t)b.size(), k,
                                                ts.data(), ts.size(), x.data.data(), TPL_MEM_HOST,
                                                on_device ? on_device->data() : nullptr));
+  return x;
+}
+// A^{-1} b by the two-pass solve with the built-in inv, stopped at the first step m* <= kmax
+// whose relative Lanczos residual (ftk::inv_residuals) is <= tol
+// (tpl_lanczos_two_pass_inv_tol): bitwise lanczos_two_pass(op, b, m*, ftk::inv()). info, if
+// given: m*, whether the tolerance was met, and the history up to the last entry formed.
+struct InvTolInfo {
+  size_t steps = 0;
+  bool converged = false;
+  std::vector<double> residuals;
+};
+inline std::vector<double> lanczos_two_pass_inv_tol(const HipCsrOp& op, const std::vector<double>& b,
+                                                    size_t kmax, double tol,
+                                                    InvTolInfo* info = nullptr) {
+  detail::check_b(op, b);
+  std::vector<double> x(op.nrows()), res(kmax ? kmax : 1);
+  size_t steps = 0, res_len = 0;
+  int32_t converged = 0;
+  detail::check(tpl_lanczos_two_pass_inv_tol(op.handle(), b.data(), (int64_t)b.size(), kmax, tol,
+                                             x.data(), TPL_MEM_HOST, &steps, &converged,
+                                             res.data(), &res_len));
+  if (info) {
+    res.resize(res_len);
+    *info = InvTolInfo{steps, converged != 0, std::move(res)};
+  }
   return x;
 }
 // One lock-step two-pass run for the s columns of B (n x s): pass one for all columns

@@ -128,6 +128,13 @@ extern "C" {
     fn tpl_lanczos_two_pass_exp_times(op: *mut TplOp, b: *const f64, b_len: i64, k: usize,
                                       ts: *const f64, m: usize, x_out: *mut f64, mem: c_int,
                                       on_device: *mut i32) -> c_int;
+    fn tpl_lanczos_two_pass_inv_tol(op: *mut TplOp, b: *const f64, b_len: i64, kmax: usize,
+                                    tol: f64, x_out: *mut f64, mem: c_int, steps: *mut usize,
+                                    converged: *mut i32, res_out: *mut f64,
+                                    res_len: *mut usize) -> c_int;
+    fn tpl_ftk_inv_residuals(alphas: *const f64, n_alphas: usize, betas: *const f64,
+                             n_betas: usize, res_out: *mut f64, res_cap: usize,
+                             res_len: *mut usize) -> c_int;
     fn tpl_op_ftk_exp_times_device(op: *mut TplOp, alphas: *const f64, n: usize,
                                    betas: *const f64, ts: *const f64, m: usize,
                                    y_out: *mut f64, on_device: *mut i32) -> c_int;
@@ -846,6 +853,59 @@ pub fn lanczos_two_pass_exp_times<O: HipOperand>(
         }
         Ok((column_major(&x, op.n, m), on.iter().map(|&v| v != 0).collect()))
     })?
+}
+
+/// What `lanczos_two_pass_inv_tol` reports beside x: the steps of the iterate it returns
+/// (m*), whether the tolerance was met, and the residual history up to the last entry formed.
+pub struct InvTolInfo {
+    pub steps: usize,
+    pub converged: bool,
+    pub residuals: Vec<f64>,
+}
+
+/// A^{-1} b by the two-pass solve with the built-in inv, stopped at the first step m* <= kmax
+/// whose relative Lanczos residual is <= `tol` (no reference counterpart): bitwise
+/// `lanczos_two_pass` with k = m* and the native inv. On one GPU within the device-inv bounds
+/// the call is one graph and the stop is taken on the device.
+pub fn lanczos_two_pass_inv_tol<O: HipOperand>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    kmax: usize,
+    tol: f64,
+    stack: &mut MemStack,
+) -> Result<(Mat<f64>, InvTolInfo), LanczosError> {
+    let _ = stack;
+    let bv = column(b);
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n];
+        let mut res = vec![0.0; kmax.max(1)];
+        let (mut steps, mut res_len, mut converged) = (0usize, 0usize, 0i32);
+        let _g = op.lock.lock().unwrap();
+        // SAFETY: b has n entries, x n, res kmax; the scalars outlive the call.
+        unsafe {
+            check(tpl_lanczos_two_pass_inv_tol(op.op, bv.as_ptr(), bv.len() as i64, kmax, tol,
+                                               x.as_mut_ptr(), TPL_MEM_HOST, &mut steps,
+                                               &mut converged, res.as_mut_ptr(), &mut res_len))?;
+        }
+        res.truncate(res_len);
+        Ok((column_major(&x, op.n, 1),
+            InvTolInfo { steps, converged: converged != 0, residuals: res }))
+    })?
+}
+
+/// The residual history of the inverse solve (`tpl_ftk_inv_residuals`): entry m - 1 is the
+/// relative Lanczos residual of the m-step iterate, m = 1 ..= min(alphas.len(), betas.len()).
+pub fn inv_residuals(alphas: &[f64], betas: &[f64]) -> Vec<f64> {
+    let mut res = vec![0.0; alphas.len().min(betas.len())];
+    let mut len = 0usize;
+    // SAFETY: the slices' own lengths; res holds min(n_alphas, n_betas) entries.
+    let rc = unsafe {
+        tpl_ftk_inv_residuals(alphas.as_ptr(), alphas.len(), betas.as_ptr(), betas.len(),
+                              res.as_mut_ptr(), res.len(), &mut len)
+    };
+    assert_eq!(rc, 0, "tpl_ftk_inv_residuals");
+    res.truncate(len);
+    res
 }
 
 /// The one-pass sibling of `lanczos_two_pass_multi`: one standard pass, one reconstruction

@@ -212,7 +212,9 @@ constexpr int kFlagBytes = 32;       // DevState::flags: 8 int32
 struct DevState {
   int32_t* flags;   // [0] stop, [1] error (1 = zero b), [2] steps_taken, [3] second
                     // Gram-Schmidt passes, [4] device f(T_k) handed back to the host,
-                    // [5] rows of T_k's LU eliminated during pass one (k_p1_axpy)
+                    // [5] rows of T_k's LU eliminated during pass one (k_p1_axpy),
+                    // [6] the tolerance stop's hit, [7] its residual entries formed
+                    // (k_p1_axpy_tol; k_p1_init leaves both alone)
   double* norms;    // [0] = ||b||, [j] = beta_j                         (kcap+1)
   double* alphas;   // alphas[j-1] = alpha_j                              (kcap)
   double* betas;    // betas[j-1]  = beta_j                               (kcap)

@@ -91,6 +91,38 @@ int tpl_ftk_inv(const double* alphas, size_t n_alphas, const double* betas, size
   return 0;
 }
 
+int tpl_ftk_inv_residuals(const double* alphas, size_t n_alphas, const double* betas,
+                           size_t n_betas, double* res_out, size_t res_cap, size_t* res_len) {
+  const size_t L = n_alphas < n_betas ? n_alphas : n_betas;
+  if (res_len) *res_len = L;
+  if (L == 0) return 0;
+  if (!alphas || !betas || !res_out || res_cap < L) return 1;
+  // tpl_ftk_inv's elimination, the running row only (the device's lu_row with more = true:
+  // d and b of the new row depend on neither `more` nor du1)
+  double d = alphas[0], du = betas[0], b = 1.0;
+  res_out[0] = std::fabs(betas[0] * (b / d));
+  for (size_t i = 0; i + 1 < L; ++i) {
+    const double dli = betas[i], du1 = betas[i + 1];
+    double dip1 = alphas[i + 1], duip1 = du1, bip1 = 0.0;
+    if (std::fabs(d) >= std::fabs(dli)) {
+      const double fact = dli / d;
+      dip1 = dip1 - fact * du;
+      bip1 = bip1 - fact * b;
+    } else {
+      const double fact = d / dli;
+      const double temp = dip1;
+      dip1 = du - fact * temp;
+      duip1 = -fact * du1;
+      bip1 = b - fact * bip1;
+    }
+    d = dip1;
+    du = duip1;
+    b = bip1;
+    res_out[i + 1] = std::fabs(du1 * (b / d));
+  }
+  return 0;
+}
+
 int tpl_ftk_sq(const double* alphas, size_t n_alphas, const double* betas, size_t n_betas,
                double* y_out, size_t y_cap, size_t* y_len, char* err_msg, size_t err_cap,
                void* /*user*/) {

@@ -3,10 +3,12 @@
 //
 // Map of the device sources (one compile unit per .hip; tpl_launch.h declares every
 // launcher, the unit holding a kernel defines its launcher):
-//   tpl_kernels.hip     k_p1_init, k_p1_spmv, k_p1_axpy (+ lu_row), k_ftk_inv (+ div_rn),
+//   tpl_kernels.hip     k_p1_init, k_p1_spmv, k_p1_axpy, k_ftk_inv (+ div_rn),
 //                       k_p2_init, k_p2_coefs, k_p2_spmv, k_p2_tail, k_gemv_recon.
 //                       k_ftk_inv stays beside k_p1_axpy: both inline lu_row, and apart
 //                       k_p1_axpy's elimination branch compiles to other registers
+//   tpl_k_p1_tol.hip    k_p1_axpy_tol, k_p1_tol_fin (pass one of the inverse solve that stops
+//                       at a residual tolerance; lu_row itself: tpl_klu.h)
 //   tpl_k_p2_cached.hip k_p2_cached (the two-pass solver's pass-two step whose long rows read
 //                       the sums its pass one kept: the long-row cache)
 //   tpl_k_spmv.hip      k_spmv (the plain product), k_permute
@@ -59,6 +61,7 @@
 // slice-7 bins one more (polling the other slices' partials).
 #define TPL_LAB_TABLE 1  // this unit holds the stamp build's table (tpl_lab.h)
 #include "tpl_klaunch.h"
+#include "tpl_klu.h"
 
 namespace tpl {
 
@@ -107,43 +110,7 @@ __global__ __launch_bounds__(kTPB, p1_min_waves(F, 1)) void k_p1_spmv(P1SpmvArgs
 // ---- T_k^{-1} e_1 on the device (the one-graph inv): the host solver's operations
 // (tpl_ftk.cpp: the LAPACK dgtsv scheme, tridiagonal elimination with partial pivoting,
 // then back substitution), bit for bit.
-// Running row i of the elimination: its pivot, super-diagonal and right-hand side.
-struct LuRow {
-  double d, du, b;
-};
-// Eliminate row i (dl = beta_i, d1 = alpha_{i+1}, du1 = beta_{i+1} or 0 when row i + 1 is
-// the last; more = row i + 2 exists): stores row i of U (D, DU, DU2) and of the
-// transformed right-hand side (B), advances `cur` to row i + 1. The operations of the
-// host loop in its order (-ffp-contract=off).
-__device__ __forceinline__ void lu_row(int i, bool more, double dli, double d1, double du1,
-                                       LuRow& cur, double* D, double* DU, double* DU2,
-                                       double* B) {
-  double dip1 = d1, duip1 = du1, bip1 = 0.0, du2i = 0.0;
-  if (fabs(cur.d) >= fabs(dli)) {
-    const double fact = dli / cur.d;
-    dip1 = dip1 - fact * cur.du;
-    bip1 = bip1 - fact * cur.b;
-    D[i] = cur.d;
-    DU[i] = cur.du;
-    B[i] = cur.b;
-  } else {
-    const double fact = cur.d / dli;
-    D[i] = dli;
-    const double temp = dip1;
-    dip1 = cur.du - fact * temp;
-    if (more) {
-      du2i = duip1;
-      duip1 = -fact * du2i;
-    }
-    DU[i] = temp;
-    B[i] = bip1;            // b[i] <- old b[i+1] (= 0: b[i+1] is first set at step i)
-    bip1 = cur.b - fact * bip1;
-  }
-  DU2[i] = du2i;
-  cur.d = dip1;
-  cur.du = duip1;
-  cur.b = bip1;
-}
+// (LuRow, lu_row: tpl_klu.h, shared with k_p1_axpy_tol.)
 // a / b given y = RN(1 / b): Markstein's correction q = RN(q0 + RN(a - b q0) y), q0 =
 // RN(a y), is the correctly rounded quotient — the IEEE division's bits — whenever no
 // intermediate leaves the normal range; elsewhere (zeros, huge or tiny magnitudes,
@@ -176,6 +143,8 @@ __device__ __forceinline__ double div_rn(double a, double b, double y, bool b_ok
 // so only the last rows and the back substitution remain after pass one (k_ftk_inv).
 // That workgroup is block a.elim_block, the one after the element grid (its padding
 // blocks included, so never one elem_block maps to a row block or to -1); -1: none.
+// k_p1_axpy_tol (tpl_k_p1_tol.hip) repeats this kernel's text with the tolerance stop added:
+// a change to the body below belongs there too.
 template <int NP>
 __global__ __launch_bounds__(kTPB) void k_p1_axpy(P1AxpyArgs a) {
   __shared__ double red[4];

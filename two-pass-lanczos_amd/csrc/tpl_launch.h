@@ -18,6 +18,13 @@ hipError_t p1_spmv(const CsrDev& A, const DevState& S, const double* xsrc, const
 hipError_t p1_axpy(const CsrDev& A, const DevState& S, const double* W, const double* r_cur,
                    double* r_next, int j, int k, int elim, hipStream_t s,
                    unsigned long long* stamp = nullptr);
+// the step of the inverse solve that stops at a residual tolerance (k_p1_axpy_tol,
+// tpl_k_p1_tol.hip): p1_axpy with the elimination workgroup, which also keeps the residual
+// history in tr = {tol, res[kcap]} and raises the stop; p1_tol_fin: after the last step,
+// one thread settles steps_taken
+hipError_t p1_axpy_tol(const CsrDev& A, const DevState& S, const double* W, const double* r_cur,
+                       double* r_next, int j, int k, double* tr, hipStream_t s);
+hipError_t p1_tol_fin(const DevState& S, double* tr, hipStream_t s);
 hipError_t p2_tail(int64_t n, const DevState& S, double* x, double* const V[3], hipStream_t s);
 hipError_t permute(int64_t n, int cols, double* out, int64_t ldo, const double* in, int64_t ldi,
                    const int32_t* idx, hipStream_t s);

@@ -200,6 +200,12 @@ struct tpl_op_s {
   // host mirror; nullptr until the first tpl_lanczos_two_pass_batch_exp_times /
   // tpl_op_ftk_exp_times_batch_device call. The times are d_exp_ts
   int32_t *d_expb_back = nullptr, *h_expb_back = nullptr;
+  // the inverse solve that stops at a residual tolerance (ensure_tol): {tol, res[tol_cap]}
+  // on the device and the pinned mirror of flags | res; nullptr until the first
+  // tpl_lanczos_two_pass_inv_tol call that takes the device path. tol_cap follows st.kcap
+  double* d_tol = nullptr;
+  void* h_tol = nullptr;
+  size_t tol_cap = 0;
   tpl::BatchBufs bat;              // lock-step batch solves (ensure_batch)
   std::map<std::pair<int, size_t>, tpl::GraphExec> graphs;
   // device allocations of this operator (pointer -> bytes): tpl_op_device_bytes
@@ -310,6 +316,11 @@ void ensure_exp_times(tpl_op_s* op);
 // Allocated on the first batch exp-times call, counted in device_bytes, freed with the
 // operator. No graph holds them.
 void ensure_exp_times_batch(tpl_op_s* op);
+// The tolerance and residual history of tpl_lanczos_two_pass_inv_tol's device path
+// (op->d_tol: 1 + kcap doubles) and the pinned mirror of flags | res, for the state's current
+// kcap (ensure_state first). Counted in device_bytes, freed with the operator; replacing them
+// drops the cached graphs, which hold the pointer (the first allocation drops nothing).
+void ensure_tol(tpl_op_s* op);
 // The interleaved work vectors, per-column state and hand-off buffers of a batch group of
 // nb (2 or 4) columns and k steps, allocated on demand and counted in device_bytes. They
 // grow with nb and k; growing drops the cached graphs. A layout rebuild frees them
@@ -397,6 +408,9 @@ void run_pass2_batch(tpl_op_s* op, size_t kmax, int nb);
 // otherwise the launch list depends on every steps_c and runs uncaptured.
 void run_pass2_batch_multi(tpl_op_s* op, const size_t* steps, int nb, size_t m);
 void run_two_pass_dev(tpl_op_s* op, size_t k, int f);
+// The one-graph inverse solve that stops at the tolerance in op->d_tol[0] (ensure_tol and
+// the upload of the tolerance and of the zeroed hit words first): one graph per kmax.
+void run_two_pass_inv_tol(tpl_op_s* op, size_t kmax);
 HostDecomp fetch_decomp(tpl_op_s* op);
 
 } // namespace tpl

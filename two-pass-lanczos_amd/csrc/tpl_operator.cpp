@@ -15,6 +15,7 @@ tpl_op_s::~tpl_op_s() {
   for (const auto& kv : allocs) hipFree(const_cast<void*>(kv.first));  // every dev_alloc
   if (st.h_state) hipHostFree(st.h_state);
   if (h_exp_back) hipHostFree(h_exp_back);
+  if (h_tol) hipHostFree(h_tol);
   if (h_expb_back) hipHostFree(h_expb_back);
   if (ev0) hipEventDestroy(ev0);
   if (ev1) hipEventDestroy(ev1);
@@ -421,6 +422,19 @@ void ensure_exp_times(tpl_op_s* op) {
   if (!op->h_exp_back)
     HIPCHK(hipHostMalloc((void**)&op->h_exp_back, TPL_MULTI_MAX * sizeof(int32_t),
                          hipHostMallocDefault));
+}
+void ensure_tol(tpl_op_s* op) {
+  const size_t kc = op->st.kcap;
+  if (op->d_tol && op->tol_cap == kc) return;
+  if (op->d_tol) drop_graphs(op);  // they hold the pointer being replaced
+  dev_free(op, op->d_tol);
+  if (op->h_tol) hipHostFree(op->h_tol);
+  op->h_tol = nullptr;
+  op->tol_cap = 0;
+  dev_alloc(op, &op->d_tol, (1 + kc) * sizeof(double));
+  HIPCHK(hipMemset(op->d_tol, 0, (1 + kc) * sizeof(double)));
+  HIPCHK(hipHostMalloc(&op->h_tol, kFlagBytes + kc * sizeof(double), hipHostMallocDefault));
+  op->tol_cap = kc;
 }
 void free_batch(tpl_op_s* op) {
   BatchBufs& b = op->bat;

@@ -24,6 +24,8 @@ enum GraphKind {
   kGPass2Batch,       // pass two of a batch group: one graph per (largest steps, NB)
   kGPass2BatchMulti,  // pass two of a batch-multi group whose columns took the same
                       // number of steps: one graph per (steps, NB, m)
+  kGTwoPassInvTol,    // one-graph inverse solve that stops at a residual tolerance: one
+                      // graph per kmax (the tolerance is device data, not an argument)
   kGLongCache = 64,   // + this: the sequence stores / reads the long-row cache (a two-pass
                       // solve with the cache on for it; other kernels, other graphs)
   kGFusedP2 = 128,    // + this: pass two is the fused one (k_p2_hub, k_p2_rows) in place of
@@ -496,6 +498,38 @@ void run_two_pass_dev(tpl_op_s* op, size_t k, int f) {
   HIPCHK(hipEventRecord(op->tev[3], op->stream));
   if (!fused) enqueue_pass2_tail(op);
   op->p2_launches = (int64_t)k - 1;
+}
+
+// The one-graph inverse solve that stops at a residual tolerance: run_two_pass_dev's graph
+// for inv with k_p1_axpy_tol in place of k_p1_axpy (the SpMV launches, the long-row cache
+// and the choice of pass two are its own), and k_p1_tol_fin between pass one and k_ftk_inv.
+// After the stop every later launch of pass one returns at its stop test, and pass two takes
+// steps_taken from the device as after a breakdown. No live timing.
+void run_two_pass_inv_tol(tpl_op_s* op, size_t kmax) {
+  const int ck = graph_cache_kind(op);
+  op->last_long_cache = kmax >= 2 && ck != 0;
+  const bool fused = fused_p2(op);
+  op->last_fused_p2 = kmax >= 2 && fused;
+  run_graph(op, kGTwoPassInvTol + ck, kmax, [&] {
+    enqueue_p1_prologue(op);
+    for (int j = 1; j <= (int)kmax; ++j) {
+      CsrDev A = csr_dev(op, true);
+      if (double* ycrow = ck ? cache_row(op, j) : nullptr) A.ypart = ycrow;
+      HIPCHK(launch::p1_spmv(A, op->st.S, rG_of(op, j), r_of(op, j),
+                             j >= 2 ? r_of(op, j - 1) : nullptr, op->W, nullptr, j, op->stream,
+                             nullptr));
+      HIPCHK(launch::p1_axpy_tol(A, op->st.S, op->W, r_of(op, j), op->R[(j + 1) % 3], j,
+                                 (int)kmax, op->d_tol, op->stream));
+    }
+    HIPCHK(launch::p1_tol_fin(op->st.S, op->d_tol, op->stream));
+    enqueue_ftk_dev(op, kmax, kDevInv);
+    if (fused) {
+      enqueue_pass2_fused(op, 0);
+    } else {
+      enqueue_pass2_dyn_steps(op, kmax);
+      enqueue_pass2_tail(op);
+    }
+  });
 }
 
 // elim: eliminate T_k's LU during the pass (a device inv follows: k_ftk_inv)

@@ -596,6 +596,83 @@ tpl_status tpl_lanczos_two_pass_exp_times(tpl_op_t op, const double* b, int64_t 
   });
 }
 
+tpl_status tpl_lanczos_two_pass_inv_tol(tpl_op_t op, const double* b, int64_t b_len, size_t kmax,
+                                        double tol, double* x_out, int mem, size_t* steps,
+                                        int32_t* converged, double* res_out, size_t* res_len) {
+  return guarded([&] {
+    if (!op || !x_out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!(tol >= 0.0)) fail(TPL_ERR_INVALID_ARGUMENT, "tol must be a number >= 0");
+    set_device(op);
+    check_b(op, b, b_len);
+    check_k(kmax);
+    auto report = [&](size_t m, bool hit, const double* res, size_t n_res) {
+      if (steps) *steps = m;
+      if (converged) *converged = hit ? 1 : 0;
+      if (res_out && n_res) std::memcpy(res_out, res, n_res * sizeof(double));
+      if (res_len) *res_len = res_out ? n_res : 0;
+    };
+    // the stop rule on a history of `formed` entries after `taken` steps: the smallest m in
+    // 1 .. taken - 1 with res[m - 1] <= tol, else taken
+    auto first_hit = [&](const double* res, size_t formed, size_t taken) -> size_t {
+      for (size_t m = 1; m < taken && m <= formed; ++m)
+        if (res[m - 1] <= tol) return m;
+      return 0;
+    };
+    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS, kmax);
+    const TimingOff untimed(op);
+    if (device_f(op, &tpl_ftk_inv, kmax) == kDevInv) {
+      // one graph: pass one watching the residual, k_ftk_inv on the m* rows, pass two
+      ensure_state(op, kmax);
+      ensure_tol(op);
+      upload_vec(op, op->b, b, mem);
+      const int32_t zero[2] = {0, 0};
+      HIPCHK(hipMemcpyAsync(op->st.S.flags + 6, zero, sizeof(zero), hipMemcpyHostToDevice,
+                            op->stream));
+      HIPCHK(hipMemcpyAsync(op->d_tol, &tol, sizeof(double), hipMemcpyHostToDevice, op->stream));
+      run_two_pass_inv_tol(op, kmax);
+      download_vec(op, x_out, op->x, 1, mem);
+      char* h = (char*)op->h_tol;
+      HIPCHK(hipMemcpyAsync(h, op->st.d_state, kFlagBytes, hipMemcpyDeviceToHost, op->stream));
+      if (kmax > 1)
+        HIPCHK(hipMemcpyAsync(h + kFlagBytes, op->d_tol + 1, (kmax - 1) * sizeof(double),
+                              hipMemcpyDeviceToHost, op->stream));
+      sync_checked(op);
+      int32_t flags[kFlagBytes / 4];
+      std::memcpy(flags, h, kFlagBytes);
+      const bool zero_x = zero_result(op, flags, x_out, mem);
+      op->last_one_graph = true;
+      const size_t formed = std::min<size_t>((size_t)flags[7], kmax - 1);
+      report((size_t)flags[2], !zero_x && flags[6] != 0, (const double*)(h + kFlagBytes), formed);
+      return;
+    }
+    // composed on the host: pass one to kmax, the history and the rule, y on the first m*
+    // rows, pass two to m* (the oracle of the device path)
+    op->last_one_graph = false;
+    run_pass_one(op, b, kmax, mem, false, false);
+    const HostDecomp d = fetch_decomp(op);
+    if (zero_result(op, d.flags, x_out, mem)) {
+      report(0, false, nullptr, 0);
+      return;
+    }
+    std::vector<double> res(d.steps);
+    size_t formed = 0;
+    tpl_ftk_inv_residuals(d.alphas, d.steps, d.betas, d.steps - 1, res.data(), res.size(),
+                          &formed);
+    const size_t hit = first_hit(res.data(), formed, d.steps);
+    const size_t m = hit ? hit : d.steps;
+    std::vector<double> y(m);
+    size_t ylen = m;
+    tpl_ftk_inv(d.alphas, m, d.betas, m - 1, y.data(), m, &ylen, nullptr, 0, nullptr);
+    for (auto& v : y) v = v * d.b_norm;
+    HIPCHK(hipMemcpyAsync(op->st.S.y, y.data(), m * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    run_pass2(op, m);
+    download_vec(op, x_out, op->x, 1, mem);
+    sync_checked(op);
+    report(m, hit != 0, res.data(), formed);
+  });
+}
+
 tpl_status tpl_op_reorth_second_passes(tpl_op_t op, int64_t* count) {
   return guarded([&] {
     if (!op || !count) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");

@@ -281,3 +281,9 @@ tpl_fused_pass_two_rows = _sig("tpl_fused_pass_two_rows", c_int, c_int64, c_void
 EXPORTED += ["tpl_op_set_fused_pass_two", "tpl_fused_pass_two_rows"]
 EXPORTED += ["tpl_ftk_exp_t", "tpl_lanczos_two_pass_exp_times", "tpl_op_ftk_exp_times_device"]
 EXPORTED += ["tpl_lanczos_two_pass_batch_exp_times", "tpl_op_ftk_exp_times_batch_device"]
+tpl_lanczos_two_pass_inv_tol = _sig("tpl_lanczos_two_pass_inv_tol", c_int, c_void_p, c_void_p,
+                                    c_int64, c_size_t, c_double, c_void_p, c_int,
+                                    POINTER(c_size_t), POINTER(c_int32), PD, POINTER(c_size_t))
+tpl_ftk_inv_residuals = _sig("tpl_ftk_inv_residuals", c_int, PD, c_size_t, PD, c_size_t, PD,
+                             c_size_t, POINTER(c_size_t))
+EXPORTED += ["tpl_lanczos_two_pass_inv_tol", "tpl_ftk_inv_residuals"]

@@ -31,6 +31,10 @@ the matrix exponential at a list of times: exp(t_i A) b for every t_i over one K
 every exp(t_i T_k) e_1 evaluated at once on the device between the two shared passes. It
 returns shape (n, m) with strides (1, n).
 
+``lanczos_two_pass_inv_tol(operator, b, kmax, tol)`` (no reference counterpart) is the inverse
+solve that stops when the Lanczos residual estimate is <= ``tol``: bitwise
+``lanczos_two_pass(operator, b, m*, "inv")`` for the first such step m* <= kmax.
+
 ``lanczos_two_pass_batch_exp_times(operator, B, k, ts)`` (no reference counterpart) is the same
 for the s columns of ``B`` in lock-step: exp(t_i A) b_c, every exp(t_i T_k) e_1 of a group of
 columns evaluated by one device launch. It returns shape (n, m, s) with strides (1, n, n m).
@@ -119,6 +123,29 @@ def lanczos_two_pass_exp_times(operator, b, k: int, ts, return_on_device: bool =
         operator.handle, bv.ptr, bv.n, k, t.ctypes.data_as(_lib.PD), m, Vec.ptr_of(x), bv.mem,
         on.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
     return (x.T, on.astype(bool)) if return_on_device else x.T
+
+
+def lanczos_two_pass_inv_tol(operator, b, kmax: int, tol: float, return_info: bool = False):
+    """A^{-1} b by the two-pass solve with the built-in inv, stopped at the first step m* whose
+    relative Lanczos residual (``ftk.inv_residuals``) is <= ``tol``, or at ``kmax``. Bitwise
+    ``lanczos_two_pass(operator, b, m*, ftk.INV)``. On one GPU within the device-inv bounds
+    (``set_device_ftk``) the whole call is one graph and the stop is taken on the device.
+    With ``return_info`` also a dict: ``steps`` (m*), ``converged`` (bool) and ``residuals``
+    (numpy: the history up to the last entry formed, at least the first
+    min(m*, steps taken by pass one - 1))."""
+    operator = as_operator(operator)
+    bv = Vec(b)
+    x = bv.empty(operator.nrows())
+    kcap = max(int(kmax), 1)
+    res = np.zeros(kcap, dtype=np.float64)
+    steps, rlen, conv = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int32(0)
+    check(_lib.tpl_lanczos_two_pass_inv_tol(
+        operator.handle, bv.ptr, bv.n, kmax, float(tol), Vec.ptr_of(x), bv.mem,
+        ctypes.byref(steps), ctypes.byref(conv), res.ctypes.data_as(_lib.PD), ctypes.byref(rlen)))
+    if not return_info:
+        return x
+    return x, {"steps": int(steps.value), "converged": bool(conv.value),
+               "residuals": res[: rlen.value].copy()}
 
 
 def lanczos_two_pass_batch(operator, B, k: int, f_tk_solver):
