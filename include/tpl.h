@@ -302,6 +302,55 @@ tpl_status tpl_lanczos_multi(tpl_op_t op, const double* b, int64_t b_len, size_t
 tpl_status tpl_lanczos_two_pass_exp_times(tpl_op_t op, const double* b, int64_t b_len, size_t k,
                                           const double* ts, size_t m, double* x_out, int mem,
                                           int32_t* on_device);
+/* (A + sigma_i I)^{-1} b for the m shifts sigmas[0..m) over one Krylov space, each stopped
+ * at the residual tolerance of tpl_lanczos_two_pass_inv_tol (an extension). The Krylov space
+ * of A + sigma I is A's and its tridiagonal is T_k + sigma I. The definition: ONE pass one of
+ * kmax steps on A (alphas, betas, steps_taken, ||b||); for shift i, a_i[j] = alphas[j] +
+ * sigmas[i] — one IEEE addition per entry, and no other expression forms a shifted entry,
+ * on the host or on the device — then res_i = tpl_ftk_inv_residuals(a_i, betas); m*_i = the
+ * smallest m in 1 .. steps_taken - 1 with res_i[m - 1] <= tol and converged[i] = 1, or
+ * m*_i = steps_taken and converged[i] = 0 if there is none; y_i = ||b|| tpl_ftk_inv on
+ * a_i[0..m*_i), betas[0..m*_i - 1); and column i of x_out (column-major n x m, leading
+ * dimension n) is bitwise tpl_lanczos_pass_two on A's decomposition cut to m*_i steps, with
+ * y_i. steps[i] = m*_i. res_out (column-major kmax x m, or NULL): the first
+ * min(m*_i, steps_taken - 1) entries of column i are bitwise the history res_i, what follows
+ * them is unspecified, res_len[i] entries were formed (0 when res_out is NULL). steps,
+ * converged, res_out and res_len may each be NULL.
+ * So: column i depends neither on m, nor on its position, nor on the other shifts; equal
+ * shifts give equal columns; with m = 1 and sigma = 0 the call returns
+ * tpl_lanczos_two_pass_inv_tol's x, steps and converged unless some alpha_j is -0 (since
+ * -0 + 0 = +0); against an operator built explicitly as A + sigma I the result agrees to
+ * rounding only, because Lanczos on A + sigma I rounds alpha differently.
+ * On a single GPU with graphs in use, in mode 1 of tpl_op_set_device_ftk up to kmax = 1365
+ * (the device inv's bound) and in mode 2 (auto) up to kmax = 64 — past that the graph's
+ * launches after the stop were measured to cost more than the host-composed path's full pass
+ * one — the call is ONE graph, cached per (kmax, m) and replayed for any
+ * tolerance and any shift values: pass one's elimination workgroup runs one lane per shift, each keeping its
+ * own history and stop, and raises the stop when every shift has met the tolerance (about
+ * two steps run past M = max m*_i; a shift that never meets it keeps the pass running to
+ * kmax); one workgroup per shift then solves on its own m*_i rows; the multi-function pass
+ * two applies term t to column i only where t < m*_i. tpl_op_flags bit 5 reads 1 afterwards,
+ * bit 8 as after tpl_lanczos_two_pass_multi (the long-row cache follows the
+ * TPL_LONG_CACHE_TWO_PASS_MULTI bit), bit 9 reads 0. The first such call adds
+ * 8 (1 + m (4 + 5 kcap)) + 8 m bytes (kcap: the state's step capacity) and a 256-byte table
+ * of column step counts to tpl_op_device_bytes. Everywhere else (mode 0, a larger kmax,
+ * TPL_NO_GRAPH=1) the call is composed on the host as defined above, with one pass two of M
+ * steps; both paths give the same bits.
+ * Errors, in this order and before any device work: NULL op, sigmas or x_out; m == 0 or
+ * m > TPL_MULTI_MAX; tol NaN or negative; a non-finite sigma_i — each
+ * TPL_ERR_INVALID_ARGUMENT. Then tpl_lanczos_two_pass_multi's: a host-only plan is refused
+ * as by every solver, a partitioned operator is TPL_ERR_UNSUPPORTED, a zero b is the single
+ * solve's input error. No live timing.
+ * Measured on one MI355X (500k block with D, kmax = 500, shifts between 1 and
+ * 100): m = 8 at tol 1e-4 takes 10.5 ms composed on the host and 10.8 ms as one graph,
+ * against 44.0 ms for eight tpl_lanczos_two_pass_inv_tol calls on explicitly shifted
+ * operators; m = 1 (m* = 116) 6.15 and 7.17 ms against 4.19 for the single solve, which has
+ * the fused pass two. At kmax = 64 the graph is 0.98-1.01 of the host-composed path.     */
+tpl_status tpl_lanczos_two_pass_shifted_inv_tol(tpl_op_t op, const double* b, int64_t b_len,
+                                                size_t kmax, const double* sigmas, size_t m,
+                                                double tol, double* x_out, int mem,
+                                                size_t* steps, int32_t* converged,
+                                                double* res_out, size_t* res_len);
 /* ---- f(A) b_1 ... f(A) b_s in one lock-step run (an extension: the reference's
  *      solvers::lanczos_two_pass takes one b) -----------------------------------------
  * The other axis: one f, s right-hand sides. Every b_c has its own Krylov space, its own
@@ -532,6 +581,13 @@ tpl_status tpl_op_ftk_device(tpl_op_t op, int which, const double* alphas, size_
 tpl_status tpl_op_ftk_exp_times_device(tpl_op_t op, const double* alphas, size_t n,
                                        const double* betas, const double* ts, size_t m,
                                        double* y_out, int32_t* on_device);
+/* The same for k_ftk_inv_shifts alone, nothing eliminated beforehand: (T_n + sigma_i I)^{-1}
+ * e_1 for the m shifts sigmas[0..m) (1 <= m <= TPL_MULTI_MAX, 1 <= n <= 1365; above:
+ * TPL_ERR_UNSUPPORTED) into y_out (host, column-major n x m, leading dimension n, unscaled).
+ * Column i is bitwise tpl_ftk_inv on (alphas + sigma_i, betas), non-finite entries included. */
+tpl_status tpl_op_ftk_inv_shifts_device(tpl_op_t op, const double* alphas, size_t n,
+                                        const double* betas, const double* sigmas, size_t m,
+                                        double* y_out);
 /* The same for k_ftk_exp_times_batch alone, on a group of nb (2 or 4) tridiagonals: column c
  * of alphas / betas at c ld, steps[c] rows of it in use (1 <= steps[c] <= min(ld, 1800); 0 or
  * above ld: TPL_ERR_INVALID_ARGUMENT, above 1800: TPL_ERR_UNSUPPORTED), the m times
@@ -598,6 +654,17 @@ tpl_status tpl_lanczos_pass_two_multi(tpl_op_t op, const double* b, int64_t b_le
                                       const double* betas, size_t n_betas, size_t steps,
                                       double b_norm, const double* y, size_t y_len, size_t m,
                                       double* x_out, int mem);
+/* tpl_lanczos_pass_two_multi with a per-column cut: column i takes only the first
+ * col_steps[i] steps (1 <= col_steps[i] <= steps; else TPL_ERR_INVALID_ARGUMENT), so it is
+ * bitwise tpl_lanczos_pass_two at steps = col_steps[i] with the first col_steps[i] entries of
+ * y's column i. y: column-major with leading dimension ldy >= steps; entries of column i at
+ * or past col_steps[i] are never used. The basis is regenerated once, to `steps`.       */
+tpl_status tpl_lanczos_pass_two_multi_cut(tpl_op_t op, const double* b, int64_t b_len,
+                                          const double* alphas, size_t n_alphas,
+                                          const double* betas, size_t n_betas, size_t steps,
+                                          double b_norm, const double* y, size_t ldy,
+                                          const size_t* col_steps, size_t m, double* x_out,
+                                          int mem);
 
 /* ---- data loader: src/utils/data_loader.rs:211-259 (load_kkt_system) ----- */
 typedef struct tpl_csr_host {

@@ -553,6 +553,38 @@ inline std::vector<double> lanczos_two_pass_inv_tol(const HipCsrOp& op, const st
   }
   return x;
 }
+// (A + sigma_i I)^{-1} b for the shifts `sigmas` by ONE two-pass run on A, each shift stopped at
+// the first step m*_i whose relative Lanczos residual (ftk::inv_residuals on alphas + sigma_i)
+// is <= tol (tpl_lanczos_two_pass_shifted_inv_tol). Column i of the n x m result is bitwise
+// algorithms::lanczos_pass_two on A's decomposition cut to m*_i steps. info, if given, holds
+// per shift: m*_i, whether the tolerance was met, and the history up to the last entry formed.
+struct ShiftedInvTolInfo {
+  std::vector<size_t> steps;
+  std::vector<bool> converged;
+  std::vector<std::vector<double>> residuals;
+};
+inline Mat lanczos_two_pass_shifted_inv_tol(const HipCsrOp& op, const std::vector<double>& b,
+                                            size_t kmax, const std::vector<double>& sigmas,
+                                            double tol, ShiftedInvTolInfo* info = nullptr) {
+  detail::check_b(op, b);
+  const size_t m = sigmas.size(), ldr = kmax ? kmax : 1;
+  Mat x(op.nrows(), m);
+  std::vector<double> res(ldr * (m ? m : 1));
+  std::vector<size_t> steps(m ? m : 1), res_len(m ? m : 1);
+  std::vector<int32_t> converged(m ? m : 1);
+  detail::check(tpl_lanczos_two_pass_shifted_inv_tol(
+      op.handle(), b.data(), (int64_t)b.size(), kmax, sigmas.data(), m, tol, x.data.data(),
+      TPL_MEM_HOST, steps.data(), converged.data(), res.data(), res_len.data()));
+  if (info) {
+    *info = ShiftedInvTolInfo{};
+    for (size_t i = 0; i < m; ++i) {
+      info->steps.push_back(steps[i]);
+      info->converged.push_back(converged[i] != 0);
+      info->residuals.emplace_back(res.begin() + i * ldr, res.begin() + i * ldr + res_len[i]);
+    }
+  }
+  return x;
+}
 // One lock-step two-pass run for the s columns of B (n x s): pass one for all columns
 // together, f(T_k) e_1 per column on the host in column order, one pass two. Column c of the
 // n x s result is bitwise lanczos_two_pass's for B's column c with f evaluated on the host.

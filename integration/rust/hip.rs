@@ -135,6 +135,19 @@ extern "C" {
     fn tpl_ftk_inv_residuals(alphas: *const f64, n_alphas: usize, betas: *const f64,
                              n_betas: usize, res_out: *mut f64, res_cap: usize,
                              res_len: *mut usize) -> c_int;
+    fn tpl_lanczos_two_pass_shifted_inv_tol(op: *mut TplOp, b: *const f64, b_len: i64,
+                                            kmax: usize, sigmas: *const f64, m: usize, tol: f64,
+                                            x_out: *mut f64, mem: c_int, steps: *mut usize,
+                                            converged: *mut i32, res_out: *mut f64,
+                                            res_len: *mut usize) -> c_int;
+    fn tpl_lanczos_pass_two_multi_cut(op: *mut TplOp, b: *const f64, b_len: i64,
+                                      alphas: *const f64, n_alphas: usize, betas: *const f64,
+                                      n_betas: usize, steps: usize, b_norm: f64, y: *const f64,
+                                      ldy: usize, col_steps: *const usize, m: usize,
+                                      x_out: *mut f64, mem: c_int) -> c_int;
+    fn tpl_op_ftk_inv_shifts_device(op: *mut TplOp, alphas: *const f64, n: usize,
+                                    betas: *const f64, sigmas: *const f64, m: usize,
+                                    y_out: *mut f64) -> c_int;
     fn tpl_op_ftk_exp_times_device(op: *mut TplOp, alphas: *const f64, n: usize,
                                    betas: *const f64, ts: *const f64, m: usize,
                                    y_out: *mut f64, on_device: *mut i32) -> c_int;
@@ -906,6 +919,110 @@ pub fn inv_residuals(alphas: &[f64], betas: &[f64]) -> Vec<f64> {
     assert_eq!(rc, 0, "tpl_ftk_inv_residuals");
     res.truncate(len);
     res
+}
+
+/// What `lanczos_two_pass_shifted_inv_tol` reports beside x, per shift: the steps of the
+/// iterate in its column (m*_i), whether the tolerance was met, and the residual history up to
+/// the last entry formed.
+pub struct ShiftedInvTolInfo {
+    pub steps: Vec<usize>,
+    pub converged: Vec<bool>,
+    pub residuals: Vec<Vec<f64>>,
+}
+
+/// (A + sigma_i I)^{-1} b for the shifts `sigmas` by ONE two-pass run on A (no reference
+/// counterpart), each shift stopped at the first step m*_i whose relative Lanczos residual
+/// (`inv_residuals` on alphas + sigma_i) is <= `tol`: column i of the n x m result is bitwise
+/// `lanczos_pass_two` on A's decomposition cut to m*_i steps. On one GPU within the device-inv
+/// bounds the call is one graph: one elimination lane per shift, the stop taken on the device.
+pub fn lanczos_two_pass_shifted_inv_tol<O: HipOperand>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    kmax: usize,
+    sigmas: &[f64],
+    tol: f64,
+    stack: &mut MemStack,
+) -> Result<(Mat<f64>, ShiftedInvTolInfo), LanczosError> {
+    let _ = stack;
+    let bv = column(b);
+    let m = sigmas.len();
+    let ldr = kmax.max(1);
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n * m];
+        let mut res = vec![0.0; ldr * m.max(1)];
+        let mut steps = vec![0usize; m.max(1)];
+        let mut res_len = vec![0usize; m.max(1)];
+        let mut converged = vec![0i32; m.max(1)];
+        let _g = op.lock.lock().unwrap();
+        // SAFETY: b has n entries, x n m, res kmax m; the per-shift arrays hold m entries.
+        unsafe {
+            check(tpl_lanczos_two_pass_shifted_inv_tol(op.op, bv.as_ptr(), bv.len() as i64, kmax,
+                                                       sigmas.as_ptr(), m, tol, x.as_mut_ptr(),
+                                                       TPL_MEM_HOST, steps.as_mut_ptr(),
+                                                       converged.as_mut_ptr(), res.as_mut_ptr(),
+                                                       res_len.as_mut_ptr()))?;
+        }
+        let residuals = (0..m).map(|i| res[i * ldr..i * ldr + res_len[i]].to_vec()).collect();
+        steps.truncate(m);
+        Ok((column_major(&x, op.n, m),
+            ShiftedInvTolInfo { steps, converged: converged[..m].iter().map(|&v| v != 0).collect(),
+                                residuals }))
+    })?
+}
+
+/// `lanczos_pass_two` for m coefficient vectors with a per-column cut
+/// (`tpl_lanczos_pass_two_multi_cut`): `y` is column-major with leading dimension `ldy`, column
+/// i takes its first `col_steps[i]` steps only and is bitwise `lanczos_pass_two` at that count.
+pub fn lanczos_pass_two_multi_cut<O: HipOperand>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    alphas: &[f64],
+    betas: &[f64],
+    steps: usize,
+    b_norm: f64,
+    y: &[f64],
+    ldy: usize,
+    col_steps: &[usize],
+) -> Result<Mat<f64>, LanczosError> {
+    let bv = column(b);
+    let m = col_steps.len();
+    assert!(y.len() >= ldy * m, "y holds fewer than ldy * m entries");
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n * m];
+        let _g = op.lock.lock().unwrap();
+        // SAFETY: the slices' own lengths; y has ldy m entries, x n m.
+        unsafe {
+            check(tpl_lanczos_pass_two_multi_cut(op.op, bv.as_ptr(), bv.len() as i64,
+                                                 alphas.as_ptr(), alphas.len(), betas.as_ptr(),
+                                                 betas.len(), steps, b_norm, y.as_ptr(), ldy,
+                                                 col_steps.as_ptr(), m, x.as_mut_ptr(),
+                                                 TPL_MEM_HOST))?;
+        }
+        Ok(column_major(&x, op.n, m))
+    })?
+}
+
+/// `k_ftk_inv_shifts` alone (`tpl_op_ftk_inv_shifts_device`): (T_n + sigma_i I)^{-1} e_1 for
+/// every shift, column-major n x m, unscaled; column i is bitwise the native inv on
+/// (alphas + sigma_i, betas).
+pub fn ftk_inv_shifts_device<O: HipOperand>(
+    operator: &O,
+    alphas: &[f64],
+    betas: &[f64],
+    sigmas: &[f64],
+) -> Result<Vec<f64>, LanczosError> {
+    let (n, m) = (alphas.len(), sigmas.len());
+    operator.with_hip_op(|op| {
+        let mut y = vec![0.0; n * m.max(1)];
+        let _g = op.lock.lock().unwrap();
+        // SAFETY: alphas has n entries, betas at least n - 1 (checked), y n m.
+        assert!(betas.len() + 1 >= n, "betas holds fewer than n - 1 entries");
+        unsafe {
+            check(tpl_op_ftk_inv_shifts_device(op.op, alphas.as_ptr(), n, betas.as_ptr(),
+                                               sigmas.as_ptr(), m, y.as_mut_ptr()))?;
+        }
+        Ok(y)
+    })?
 }
 
 /// The one-pass sibling of `lanczos_two_pass_multi`: one standard pass, one reconstruction

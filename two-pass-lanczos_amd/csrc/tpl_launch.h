@@ -25,6 +25,36 @@ hipError_t p1_axpy(const CsrDev& A, const DevState& S, const double* W, const do
 hipError_t p1_axpy_tol(const CsrDev& A, const DevState& S, const double* W, const double* r_cur,
                        double* r_next, int j, int k, double* tr, hipStream_t s);
 hipError_t p1_tol_fin(const DevState& S, double* tr, hipStream_t s);
+// ---- the shifted inverse solve that stops each shift at a tolerance (tpl_k_p1_stol.hip).
+// The per-shift state of its device path, shift-interleaved: entry (row i, shift s) of an
+// array sits at i m + s, so a step's m stores are adjacent.
+struct ShiftTol {
+  const double* tol;   // [0]: the tolerance
+  const double* sig;   // the m shifts
+  double* lu;          // D | DU | DU2 | B of every T_k + sig[s] I: kcap rows of m each
+  double* st;          // the running rows: d | du | b, m each
+  double* res;         // the residual histories: kcap rows of m
+  int32_t* hits;       // m*_s, 0: shift s has not met the tolerance
+  int32_t* nres;       // entries of shift s's history formed
+  int32_t m, kcap;
+};
+// p1_axpy_tol with one elimination lane per shift (k_p1_axpy_stol): the stop is raised when
+// every shift has met the tolerance, with M = max m*_s in flags[6]. p1_stol_fin: after the
+// last step, one wave settles steps_taken and the history of a two-step pass.
+hipError_t p1_axpy_stol(const CsrDev& A, const DevState& S, const double* W, const double* r_cur,
+                        double* r_next, int j, int k, const ShiftTol& t, hipStream_t s);
+hipError_t p1_stol_fin(const DevState& S, const ShiftTol& t, hipStream_t s);
+// (T_n + sig[s] I)^{-1} e_1 with n = m*_s (t.hits[s], or steps_taken), one workgroup per shift
+// (k_ftk_inv_shifts): column s of Y (columns ldy >= k apart), times ||b|| when `scale`, and
+// cs[s] = n. k: the steps asked for (it sizes the LDS). Rows [0, flags[5]) of t.lu count as
+// eliminated: with flags[5] = 0 and t.hits zeroed the kernel reads neither t.lu nor t.st
+hipError_t ftk_inv_shifts(const DevState& S, int k, const ShiftTol& t, double* Y, int ldy,
+                          int32_t* cs, int scale, hipStream_t s);
+// p2_xacc with a per-column cut (k_p2_xacc_cut): term t of column c only where t < cs[c],
+// cs read on the device
+hipError_t p2_xacc_cut(const CsrDev& A, const double* Y, int ldy, int j, int nflush,
+                       const int32_t* cs, const double* vp, const double* vc, const double* vn,
+                       double* X, int64_t ldx, int m, hipStream_t s);
 hipError_t p2_tail(int64_t n, const DevState& S, double* x, double* const V[3], hipStream_t s);
 hipError_t permute(int64_t n, int cols, double* out, int64_t ldo, const double* in, int64_t ldi,
                    const int32_t* idx, hipStream_t s);

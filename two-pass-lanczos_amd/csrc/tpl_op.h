@@ -206,6 +206,17 @@ struct tpl_op_s {
   double* d_tol = nullptr;
   void* h_tol = nullptr;
   size_t tol_cap = 0;
+  // the step counts of a pass two with a per-column cut (ensure_col_steps: TPL_MULTI_MAX
+  // int32, uploaded by the host-composed paths, written by k_ftk_inv_shifts on the device
+  // path); nullptr until the first such call. No graph outlives it
+  int32_t* d_col_steps = nullptr;
+  // the shifted inverse solve that stops each shift at a tolerance (ensure_stol): one
+  // allocation {tol, sig[m], st[3 m], lu[4 kcap m], res[kcap m]} doubles, then {hits[m],
+  // nres[m]} int32, for stol_m shifts and stol_cap steps, and the pinned mirror of
+  // flags | hits | nres | res; nullptr until the first call that needs them
+  double* d_stol = nullptr;
+  void* h_stol = nullptr;
+  size_t stol_m = 0, stol_cap = 0;
   tpl::BatchBufs bat;              // lock-step batch solves (ensure_batch)
   std::map<std::pair<int, size_t>, tpl::GraphExec> graphs;
   // device allocations of this operator (pointer -> bytes): tpl_op_device_bytes
@@ -321,6 +332,16 @@ void ensure_exp_times_batch(tpl_op_s* op);
 // kcap (ensure_state first). Counted in device_bytes, freed with the operator; replacing them
 // drops the cached graphs, which hold the pointer (the first allocation drops nothing).
 void ensure_tol(tpl_op_s* op);
+// The device table of column step counts (op->d_col_steps: TPL_MULTI_MAX int32, 256 bytes),
+// allocated on the first call that cuts pass two per column, counted in device_bytes, freed
+// with the operator.
+void ensure_col_steps(tpl_op_s* op);
+// The per-shift state of tpl_lanczos_two_pass_shifted_inv_tol's device path and of
+// tpl_op_ftk_inv_shifts_device (op->d_stol, op->h_stol) for m shifts and the state's current
+// kcap (ensure_state first): 8 (1 + m (4 + 5 kcap)) + 8 m bytes, counted in device_bytes.
+// They grow with m and follow kcap; replacing them drops the cached graphs, which hold the
+// pointers (the first allocation drops nothing). -> the kernels' view for this call's m.
+launch::ShiftTol ensure_stol(tpl_op_s* op, size_t m);
 // The interleaved work vectors, per-column state and hand-off buffers of a batch group of
 // nb (2 or 4) columns and k steps, allocated on demand and counted in device_bytes. They
 // grow with nb and k; growing drops the cached graphs. A layout rebuild frees them
@@ -397,6 +418,10 @@ void run_pass2(tpl_op_s* op, size_t steps);
 // Pass two for the m coefficient columns of op->d_Y into op->d_X (ensure_multi): one graph
 // per (steps, m).
 void run_pass2_multi(tpl_op_s* op, size_t steps, size_t m);
+// The same with a per-column cut: column i takes the terms below op->d_col_steps[i] only
+// (k_p2_xacc_cut; 1 <= that count <= steps), so it holds the bits of the single pass two at
+// that many steps. One graph per (steps, m): the counts are device data.
+void run_pass2_multi_cut(tpl_op_s* op, size_t steps, size_t m);
 // One group of a batch solve (ensure_batch first; the group's b interleaved in op->bat.b):
 // pass one for the nb columns in lock-step, one graph per (k, nb); pass
 // two up to the group's largest steps_taken, one graph per (kmax, nb).
@@ -411,6 +436,10 @@ void run_two_pass_dev(tpl_op_s* op, size_t k, int f);
 // The one-graph inverse solve that stops at the tolerance in op->d_tol[0] (ensure_tol and
 // the upload of the tolerance and of the zeroed hit words first): one graph per kmax.
 void run_two_pass_inv_tol(tpl_op_s* op, size_t kmax);
+// The one-graph shifted inverse solve (tolerance, shifts and zeroed hit tables uploaded
+// first): pass one with k_p1_axpy_stol, k_p1_stol_fin, k_ftk_inv_shifts into op->d_Y and
+// op->d_col_steps, the multi-function pass two with the cut. One graph per (kmax, m).
+void run_two_pass_shifted_inv_tol(tpl_op_s* op, size_t kmax, const launch::ShiftTol& t);
 HostDecomp fetch_decomp(tpl_op_s* op);
 
 } // namespace tpl

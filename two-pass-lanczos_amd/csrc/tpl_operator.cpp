@@ -16,6 +16,7 @@ tpl_op_s::~tpl_op_s() {
   if (st.h_state) hipHostFree(st.h_state);
   if (h_exp_back) hipHostFree(h_exp_back);
   if (h_tol) hipHostFree(h_tol);
+  if (h_stol) hipHostFree(h_stol);
   if (h_expb_back) hipHostFree(h_expb_back);
   if (ev0) hipEventDestroy(ev0);
   if (ev1) hipEventDestroy(ev1);
@@ -435,6 +436,45 @@ void ensure_tol(tpl_op_s* op) {
   HIPCHK(hipMemset(op->d_tol, 0, (1 + kc) * sizeof(double)));
   HIPCHK(hipHostMalloc(&op->h_tol, kFlagBytes + kc * sizeof(double), hipHostMallocDefault));
   op->tol_cap = kc;
+}
+void ensure_col_steps(tpl_op_s* op) {
+  if (op->d_col_steps) return;
+  dev_alloc(op, &op->d_col_steps, TPL_MULTI_MAX * sizeof(int32_t));
+  HIPCHK(hipMemset(op->d_col_steps, 0, TPL_MULTI_MAX * sizeof(int32_t)));
+}
+launch::ShiftTol ensure_stol(tpl_op_s* op, size_t m) {
+  const size_t kc = op->st.kcap;
+  if (!op->d_stol || op->stol_cap != kc || op->stol_m < m) {
+    const size_t mc = std::max(m, op->stol_m);
+    if (op->d_stol) drop_graphs(op);  // they hold the pointers being replaced
+    dev_free(op, op->d_stol);
+    if (op->h_stol) hipHostFree(op->h_stol);
+    op->h_stol = nullptr;
+    op->stol_m = op->stol_cap = 0;
+    const size_t doubles = 1 + mc * (4 + 5 * kc);
+    const size_t bytes = doubles * sizeof(double) + 2 * mc * sizeof(int32_t);
+    dev_alloc(op, &op->d_stol, bytes);
+    HIPCHK(hipMemset(op->d_stol, 0, bytes));
+    HIPCHK(hipHostMalloc(&op->h_stol,
+                         kFlagBytes + 2 * mc * sizeof(int32_t) + kc * mc * sizeof(double),
+                         hipHostMallocDefault));
+    op->stol_m = mc;
+    op->stol_cap = kc;
+  }
+  // the arrays are laid out for the capacity; their inner stride is this call's m
+  const size_t mc = op->stol_m;
+  launch::ShiftTol t{};
+  double* p = op->d_stol;
+  t.tol = p;
+  t.sig = p + 1;
+  t.st = p + 1 + mc;
+  t.lu = p + 1 + 4 * mc;
+  t.res = t.lu + 4 * kc * mc;
+  t.hits = reinterpret_cast<int32_t*>(t.res + kc * mc);
+  t.nres = t.hits + mc;
+  t.m = (int32_t)m;
+  t.kcap = (int32_t)kc;
+  return t;
 }
 void free_batch(tpl_op_s* op) {
   BatchBufs& b = op->bat;

@@ -26,6 +26,10 @@ enum GraphKind {
                       // number of steps: one graph per (steps, NB, m)
   kGTwoPassInvTol,    // one-graph inverse solve that stops at a residual tolerance: one
                       // graph per kmax (the tolerance is device data, not an argument)
+  kGPass2MultiCut,    // pass two of a multi-function solve with a per-column cut: one graph
+                      // per (steps, m) (the columns' step counts are device data)
+  kGTwoPassShiftedInvTol,  // one-graph shifted inverse solve that stops each shift at a
+                      // tolerance: one graph per (kmax, m) (tolerance and shifts: device data)
   kGLongCache = 64,   // + this: the sequence stores / reads the long-row cache (a two-pass
                       // solve with the cache on for it; other kernels, other graphs)
   kGFusedP2 = 128,    // + this: pass two is the fused one (k_p2_hub, k_p2_rows) in place of
@@ -337,6 +341,70 @@ void run_pass2_multi(tpl_op_s* op, size_t steps, size_t m) {
   op->last_long_cache = steps >= 2 && long_cache_steps(op) > 0;
   run_graph(op, kGPass2Multi + graph_cache_kind(op), steps * (TPL_MULTI_MAX + 1) + m,
             [&] { enqueue_pass2_multi(op, steps, m); });
+}
+
+// The same with a per-column cut (tpl_lanczos_pass_two_multi_cut and the shifted inverse
+// solve): k_p2_xacc_cut in place of k_p2_xacc, the columns' step counts in op->d_col_steps.
+// dyn: the one-graph solve — `steps` is the count asked for, the step records take their
+// activity from the device-held count, and x is flushed at multiples of 3 and once after the
+// last launch (the cut covers the ragged end); else the host schedule for `steps` (p2_flush).
+// The terms a column gets, and their order, are the same either way.
+static void enqueue_pass2_multi_cut(tpl_op_s* op, size_t steps, size_t m, bool dyn) {
+  const CsrDev A = csr_dev(op);
+  const int ldy = (int)op->ycap;
+  HIPCHK(launch::p2_minit(A, op->st.S, op->d_Y, ldy, op->b, op->V2[1], op->d_X, op->ld, (int)m,
+                          op->stream));
+  HIPCHK(launch::p2_coefs(op->st.S, (int)steps, dyn ? 1 : 0, op->stream));
+  for (int j = 1; j < (int)steps; ++j) {
+    launch_p2_step(op, A, j, j, 0, nullptr);
+    const int nflush = p2_flush(j, (int)steps - 1);
+    if (!nflush) continue;
+    const P2Rot v = p2_rot(op, j);
+    for (size_t c0 = 0; c0 < m; c0 += 8)
+      HIPCHK(launch::p2_xacc_cut(A, op->d_Y + c0 * op->ycap, ldy, j, nflush,
+                                 op->d_col_steps + c0, v.prev, v.cur, v.next,
+                                 op->d_X + c0 * (size_t)op->ld, op->ld,
+                                 (int)std::min<size_t>(8, m - c0), op->stream));
+  }
+}
+static void check_multi_cut(const tpl_op_s* op, size_t steps, size_t m) {
+  if (op->dist) fail(TPL_ERR_UNSUPPORTED, "multi-function solve of a partitioned operator");
+  if (m == 0 || m > op->xcols || steps > op->ycap || m > TPL_MULTI_MAX || !op->d_col_steps)
+    fail(TPL_ERR_INVALID_ARGUMENT, "run_pass2_multi_cut: buffers smaller than the request");
+}
+void run_pass2_multi_cut(tpl_op_s* op, size_t steps, size_t m) {
+  check_multi_cut(op, steps, m);
+  op->last_long_cache = steps >= 2 && long_cache_steps(op) > 0;
+  run_graph(op, kGPass2MultiCut + graph_cache_kind(op), steps * (TPL_MULTI_MAX + 1) + m,
+            [&] { enqueue_pass2_multi_cut(op, steps, m, false); });
+}
+
+// The one-graph shifted inverse solve: run_two_pass_inv_tol's pass one with k_p1_axpy_stol
+// and k_p1_stol_fin, every (T + sigma_s I)^{-1} e_1 at its own m*_s by k_ftk_inv_shifts into
+// the coefficient table, then the multi-function pass two with the cut. After the stop (every
+// shift met the tolerance) the later launches of pass one return at their stop test, the step
+// launches of pass two past M are inactive and the flush launches past M return at once.
+void run_two_pass_shifted_inv_tol(tpl_op_s* op, size_t kmax, const launch::ShiftTol& t) {
+  const size_t m = (size_t)t.m;
+  check_multi_cut(op, kmax, m);
+  const int ck = graph_cache_kind(op);
+  op->last_long_cache = kmax >= 2 && ck != 0;
+  run_graph(op, kGTwoPassShiftedInvTol + ck, kmax * (TPL_MULTI_MAX + 1) + m, [&] {
+    enqueue_p1_prologue(op);
+    for (int j = 1; j <= (int)kmax; ++j) {
+      CsrDev A = csr_dev(op, true);
+      if (double* ycrow = ck ? cache_row(op, j) : nullptr) A.ypart = ycrow;
+      HIPCHK(launch::p1_spmv(A, op->st.S, rG_of(op, j), r_of(op, j),
+                             j >= 2 ? r_of(op, j - 1) : nullptr, op->W, nullptr, j, op->stream,
+                             nullptr));
+      HIPCHK(launch::p1_axpy_stol(A, op->st.S, op->W, r_of(op, j), op->R[(j + 1) % 3], j,
+                                  (int)kmax, t, op->stream));
+    }
+    HIPCHK(launch::p1_stol_fin(op->st.S, t, op->stream));
+    HIPCHK(launch::ftk_inv_shifts(op->st.S, (int)kmax, t, op->d_Y, (int)op->ycap,
+                                  op->d_col_steps, 1, op->stream));
+    enqueue_pass2_multi_cut(op, kmax, m, true);
+  });
 }
 
 // ---- lock-step batch groups (tpl_lanczos_two_pass_batch): the single solve's launch

@@ -673,6 +673,242 @@ tpl_status tpl_lanczos_two_pass_inv_tol(tpl_op_t op, const double* b, int64_t b_
   });
 }
 
+} // extern "C"
+
+// ---- (A + sigma_i I)^{-1} b for m shifts, each stopped at the tolerance ------------------
+namespace {
+// What the definition gives for one shift on pass one's decomposition: the shifted diagonal
+// (alphas[j] + sigma, one addition per entry), its residual history, the stop rule, and
+// y = ||b|| tpl_ftk_inv on the first m* rows.
+struct ShiftedCol {
+  size_t steps = 0;
+  bool converged = false;
+  std::vector<double> res, y;
+};
+ShiftedCol shifted_col(const HostDecomp& d, double sigma, double tol) {
+  ShiftedCol c;
+  std::vector<double> a(d.steps);
+  for (size_t j = 0; j < d.steps; ++j) a[j] = d.alphas[j] + sigma;
+  c.res.resize(d.steps);
+  size_t formed = 0;
+  tpl_ftk_inv_residuals(a.data(), d.steps, d.betas, d.steps - 1, c.res.data(), c.res.size(),
+                        &formed);
+  c.res.resize(formed);
+  c.steps = d.steps;
+  for (size_t m = 1; m < d.steps && m <= formed; ++m)
+    if (c.res[m - 1] <= tol) {
+      c.steps = m;
+      c.converged = true;
+      break;
+    }
+  c.y.resize(c.steps);
+  size_t ylen = c.steps;
+  tpl_ftk_inv(a.data(), c.steps, d.betas, c.steps - 1, c.y.data(), c.steps, &ylen, nullptr, 0,
+              nullptr);
+  for (auto& v : c.y) v = v * d.b_norm;
+  return c;
+}
+// The m column step counts into op->d_col_steps.
+void upload_col_steps(tpl_op_s* op, const int32_t* cs, size_t m) {
+  ensure_col_steps(op);
+  HIPCHK(hipMemcpyAsync(op->d_col_steps, cs, m * sizeof(int32_t), hipMemcpyHostToDevice,
+                        op->stream));
+}
+// Auto mode takes the one-graph path up to this kmax, the largest at which it was measured no
+// slower than the host-composed path at every m (500k block with D, shifts 1 .. 100, m = 1,
+// 4, 8, tol 1e-4 and 1e-8, profiles/shifted_inv_tol_timing.txt: 0.98-1.01 of it at kmax =
+// 64). Past it the graph's launches after the stop — two of pass one and 4/3 of pass two per
+// step not taken, 3.5 us each — cost more than the host path's pass one run to kmax: 1.04,
+// 1.08 and 1.17 of the host path at kmax = 125, 250, 500 for one shift that stops at 116, and
+// 1.01-1.02 at kmax = 500 for every m even where a shift never stops. Mode 1 still takes the
+// graph up to the device inv's bound.
+constexpr size_t kShiftedAutoK = 64;
+// The one-graph path: where tpl_lanczos_two_pass_inv_tol takes its own, within the line
+// above in auto mode, and only where the sequence can be captured.
+bool shifted_on_device(const tpl_op_s* op, size_t kmax) {
+  return device_f(op, &tpl_ftk_inv, kmax) == kDevInv &&
+         (op->device_ftk == 1 || kmax <= kShiftedAutoK) && use_graphs() && !op->eager;
+}
+} // namespace
+
+extern "C" {
+
+tpl_status tpl_lanczos_two_pass_shifted_inv_tol(tpl_op_t op, const double* b, int64_t b_len,
+                                                size_t kmax, const double* sigmas, size_t m,
+                                                double tol, double* x_out, int mem,
+                                                size_t* steps, int32_t* converged,
+                                                double* res_out, size_t* res_len) {
+  return guarded([&] {
+    if (!op || !sigmas || !x_out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (m == 0 || m > (size_t)TPL_MULTI_MAX)
+      fail(TPL_ERR_INVALID_ARGUMENT, "m must be between 1 and TPL_MULTI_MAX");
+    if (!(tol >= 0.0)) fail(TPL_ERR_INVALID_ARGUMENT, "tol must be a number >= 0");
+    for (size_t i = 0; i < m; ++i)
+      if (!std::isfinite(sigmas[i]))
+        fail(TPL_ERR_INVALID_ARGUMENT, "every shift sigma_i must be finite");
+    set_device(op);
+    if (op->dist) fail(TPL_ERR_UNSUPPORTED, "multi-function solve of a partitioned operator");
+    check_b(op, b, b_len);
+    check_k(kmax);
+    const TimingOff untimed(op);
+    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS_MULTI);
+    auto report = [&](size_t i, size_t ms, bool hit, size_t n_res) {
+      if (steps) steps[i] = ms;
+      if (converged) converged[i] = hit ? 1 : 0;
+      if (res_len) res_len[i] = res_out ? n_res : 0;
+    };
+    ensure_state(op, kmax);
+    ensure_multi(op, m);
+    ensure_col_steps(op);
+    if (shifted_on_device(op, kmax)) {
+      // one graph: pass one with a lane per shift, every y_i on its own m*_i rows, pass two
+      const launch::ShiftTol t = ensure_stol(op, m);
+      upload_vec(op, op->b, b, mem);
+      const int32_t zero[2] = {0, 0};
+      HIPCHK(hipMemcpyAsync(op->st.S.flags + 6, zero, sizeof(zero), hipMemcpyHostToDevice,
+                            op->stream));
+      HIPCHK(hipMemsetAsync(t.hits, 0, 2 * op->stol_m * sizeof(int32_t), op->stream));
+      HIPCHK(hipMemcpyAsync(op->d_stol, &tol, sizeof(double), hipMemcpyHostToDevice, op->stream));
+      HIPCHK(hipMemcpyAsync(op->d_stol + 1, sigmas, m * sizeof(double), hipMemcpyHostToDevice,
+                            op->stream));
+      run_two_pass_shifted_inv_tol(op, kmax, t);
+      download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+      char* h = (char*)op->h_stol;
+      int32_t* h_hits = (int32_t*)(h + kFlagBytes);
+      double* h_res = (double*)(h + kFlagBytes + 2 * op->stol_m * sizeof(int32_t));
+      HIPCHK(hipMemcpyAsync(h, op->st.d_state, kFlagBytes, hipMemcpyDeviceToHost, op->stream));
+      HIPCHK(hipMemcpyAsync(h_hits, t.hits, 2 * op->stol_m * sizeof(int32_t),
+                            hipMemcpyDeviceToHost, op->stream));
+      if (res_out && kmax > 1)
+        HIPCHK(hipMemcpyAsync(h_res, t.res, (kmax - 1) * m * sizeof(double),
+                              hipMemcpyDeviceToHost, op->stream));
+      sync_checked(op);
+      int32_t flags[kFlagBytes / 4];
+      std::memcpy(flags, h, kFlagBytes);
+      op->last_one_graph = true;
+      if (flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+      if (flags[2] == 0) {
+        zero_out_cols(op, x_out, m, mem);
+        for (size_t i = 0; i < m; ++i) report(i, 0, false, 0);
+        return;
+      }
+      const int32_t* h_nres = h_hits + op->stol_m;
+      for (size_t i = 0; i < m; ++i) {
+        const size_t formed = std::min<size_t>((size_t)h_nres[i], kmax - 1);
+        if (res_out)
+          for (size_t r = 0; r < formed; ++r) res_out[i * kmax + r] = h_res[r * m + i];
+        report(i, h_hits[i] ? (size_t)h_hits[i] : (size_t)flags[2], h_hits[i] != 0, formed);
+      }
+      return;
+    }
+    // composed on the host (the oracle of the device path): pass one to kmax, then per shift
+    // the history, the rule and y on the first m*_i rows, one pass two of M = max m*_i steps
+    op->last_one_graph = false;
+    run_pass_one(op, b, kmax, mem, false, false);
+    const HostDecomp d = fetch_decomp(op);
+    if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+    if (d.steps == 0) {
+      zero_out_cols(op, x_out, m, mem);
+      for (size_t i = 0; i < m; ++i) report(i, 0, false, 0);
+      return;
+    }
+    std::vector<double> Y(m * d.steps, 0.0);
+    int32_t cs[TPL_MULTI_MAX];
+    size_t M = 0;
+    for (size_t i = 0; i < m; ++i) {
+      const ShiftedCol c = shifted_col(d, sigmas[i], tol);
+      std::copy(c.y.begin(), c.y.end(), Y.begin() + i * d.steps);
+      cs[i] = (int32_t)c.steps;
+      M = std::max(M, c.steps);
+      if (res_out) std::copy(c.res.begin(), c.res.end(), res_out + i * kmax);
+      report(i, c.steps, c.converged, c.res.size());
+    }
+    upload_y(op, Y.data(), d.steps, M, m);
+    upload_col_steps(op, cs, m);
+    run_pass2_multi_cut(op, M, m);
+    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+    sync_checked(op);
+  });
+}
+
+tpl_status tpl_lanczos_pass_two_multi_cut(tpl_op_t op, const double* b, int64_t b_len,
+                                          const double* alphas, size_t n_alphas,
+                                          const double* betas, size_t n_betas, size_t steps,
+                                          double b_norm, const double* y, size_t ldy,
+                                          const size_t* col_steps, size_t m, double* x_out,
+                                          int mem) {
+  return guarded([&] {
+    check_multi(op, x_out != nullptr && col_steps != nullptr && y != nullptr, m);
+    check_b(op, b, b_len);
+    if (steps == 0 || ldy < steps || steps > (size_t)INT32_MAX / 2)
+      fail(TPL_ERR_INVALID_ARGUMENT, "steps must be >= 1 and ldy >= steps");
+    int32_t cs[TPL_MULTI_MAX];
+    for (size_t i = 0; i < m; ++i) {
+      if (col_steps[i] < 1 || col_steps[i] > steps)
+        fail(TPL_ERR_INVALID_ARGUMENT, "every col_steps[i] must be between 1 and steps");
+      cs[i] = (int32_t)col_steps[i];
+    }
+    if (b_norm <= kBreakdownTol)
+      fail_input("The initial vector `b` must not be a zero vector.");
+    if (n_alphas < steps || n_betas + 1 < steps || !alphas || (steps > 1 && !betas))
+      fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
+    ensure_state(op, steps);
+    ensure_multi(op, m);
+    const DevState& S = op->st.S;
+    HIPCHK(hipMemcpyAsync(S.norms, &b_norm, sizeof(double), hipMemcpyHostToDevice, op->stream));
+    HIPCHK(hipMemcpyAsync(S.alphas, alphas, steps * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    if (steps > 1)
+      HIPCHK(hipMemcpyAsync(S.betas, betas, (steps - 1) * sizeof(double), hipMemcpyHostToDevice,
+                            op->stream));
+    upload_y(op, y, ldy, steps, m);
+    upload_col_steps(op, cs, m);
+    upload_vec(op, op->b, b, mem);
+    run_pass2_multi_cut(op, steps, m);
+    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+    sync_checked(op);
+  });
+}
+
+tpl_status tpl_op_ftk_inv_shifts_device(tpl_op_t op, const double* alphas, size_t n,
+                                        const double* betas, const double* sigmas, size_t m,
+                                        double* y_out) {
+  return guarded([&] {
+    if (!op || !alphas || !sigmas || !y_out || (n > 1 && !betas))
+      fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (m == 0 || m > (size_t)TPL_MULTI_MAX)
+      fail(TPL_ERR_INVALID_ARGUMENT, "m must be between 1 and TPL_MULTI_MAX");
+    if (n == 0) fail(TPL_ERR_INVALID_ARGUMENT, "n must be >= 1");
+    if (n > kDevFtkMaxK) fail(TPL_ERR_UNSUPPORTED, "k above the device f(T_k) bound");
+    set_device(op);
+    if (op->dist) fail(TPL_ERR_UNSUPPORTED, "multi-function solve of a partitioned operator");
+    ensure_state(op, n);
+    ensure_multi(op, m);
+    ensure_col_steps(op);
+    const launch::ShiftTol t = ensure_stol(op, m);
+    // the solver state as pass one leaves it: steps_taken = n, ||b|| = 1, no error, no row
+    // eliminated, no shift stopped
+    const int32_t flags[kFlagBytes / 4] = {0, 0, (int32_t)n, 0, 0, 0, 0, 0};
+    const double one = 1.0;
+    const DevState& S = op->st.S;
+    HIPCHK(hipMemcpyAsync(S.flags, flags, kFlagBytes, hipMemcpyHostToDevice, op->stream));
+    HIPCHK(hipMemcpyAsync(S.norms, &one, sizeof(double), hipMemcpyHostToDevice, op->stream));
+    HIPCHK(hipMemcpyAsync(S.alphas, alphas, n * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    if (n > 1)
+      HIPCHK(hipMemcpyAsync(S.betas, betas, (n - 1) * sizeof(double), hipMemcpyHostToDevice,
+                            op->stream));
+    HIPCHK(hipMemsetAsync(t.hits, 0, 2 * op->stol_m * sizeof(int32_t), op->stream));
+    HIPCHK(hipMemcpyAsync(op->d_stol + 1, sigmas, m * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    HIPCHK(launch::ftk_inv_shifts(S, (int)n, t, op->d_Y, (int)op->ycap, op->d_col_steps, 0,
+                                  op->stream));
+    HIPCHK(hipMemcpy2DAsync(y_out, n * sizeof(double), op->d_Y, op->ycap * sizeof(double),
+                            n * sizeof(double), m, hipMemcpyDeviceToHost, op->stream));
+    sync_checked(op);
+  });
+}
+
 tpl_status tpl_op_reorth_second_passes(tpl_op_t op, int64_t* count) {
   return guarded([&] {
     if (!op || !count) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");

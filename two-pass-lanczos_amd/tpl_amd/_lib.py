@@ -287,3 +287,14 @@ tpl_lanczos_two_pass_inv_tol = _sig("tpl_lanczos_two_pass_inv_tol", c_int, c_voi
 tpl_ftk_inv_residuals = _sig("tpl_ftk_inv_residuals", c_int, PD, c_size_t, PD, c_size_t, PD,
                              c_size_t, POINTER(c_size_t))
 EXPORTED += ["tpl_lanczos_two_pass_inv_tol", "tpl_ftk_inv_residuals"]
+tpl_lanczos_two_pass_shifted_inv_tol = _sig(
+    "tpl_lanczos_two_pass_shifted_inv_tol", c_int, c_void_p, c_void_p, c_int64, c_size_t, PD,
+    c_size_t, c_double, c_void_p, c_int, POINTER(c_size_t), POINTER(c_int32), PD,
+    POINTER(c_size_t))
+tpl_lanczos_pass_two_multi_cut = _sig(
+    "tpl_lanczos_pass_two_multi_cut", c_int, c_void_p, c_void_p, c_int64, PD, c_size_t, PD,
+    c_size_t, c_size_t, c_double, PD, c_size_t, POINTER(c_size_t), c_size_t, c_void_p, c_int)
+tpl_op_ftk_inv_shifts_device = _sig("tpl_op_ftk_inv_shifts_device", c_int, c_void_p, PD,
+                                    c_size_t, PD, PD, c_size_t, PD)
+EXPORTED += ["tpl_lanczos_two_pass_shifted_inv_tol", "tpl_lanczos_pass_two_multi_cut",
+             "tpl_op_ftk_inv_shifts_device"]

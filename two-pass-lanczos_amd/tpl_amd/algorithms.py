@@ -12,6 +12,7 @@ this module                            reference
 ``lanczos_pass_two``                   src/algorithms/lanczos_two_pass.rs:128-140
 ``lanczos_pass_two_with_basis``        src/algorithms/lanczos_two_pass.rs:149-166
 ``lanczos_pass_two_multi``             (none: pass two for m coefficient vectors at once)
+``lanczos_pass_two_multi_cut``         (none: the same, column i cut to its own step count)
 ``lanczos_pass_one_batch``             (none: pass one for s vectors b in lock-step)
 ``lanczos_pass_two_batch``             (none: pass two for s vectors b in lock-step)
 ``lanczos_pass_two_batch_multi``       (none: the same for m coefficient vectors per b)
@@ -207,6 +208,34 @@ def lanczos_pass_two_multi(operator, b, decomposition: LanczosDecomposition, Y):
         bb.ctypes.data_as(POINTER(c_double)), bb.shape[0], int(decomposition.steps_taken),
         float(decomposition.b_norm), yt.ctypes.data_as(POINTER(c_double)), y_len, m,
         Vec.ptr_of(x), bv.mem))
+    return x.T
+
+
+def lanczos_pass_two_multi_cut(operator, b, decomposition: LanczosDecomposition, Y, col_steps):
+    """``lanczos_pass_two_multi`` with a per-column cut: column i takes only the first
+    ``col_steps[i]`` steps (1 <= col_steps[i] <= steps), so it is bitwise ``lanczos_pass_two``
+    on the decomposition cut to ``col_steps[i]`` steps with ``Y[:col_steps[i], i]``; the rest
+    of ``Y``'s column i is never used. Returns shape (n, m) with strides (1, n)."""
+    y = Y.detach().double().cpu().numpy() if hasattr(Y, "is_cuda") else np.asarray(Y, dtype=np.float64)
+    if y.ndim != 2:
+        raise ValueError("Y must be a (steps, m) matrix")
+    ldy, m = y.shape
+    cs = [int(c) for c in col_steps]
+    if m == 0 or len(cs) != m:
+        raise ValueError("Y must hold at least one column and col_steps one entry per column")
+    if min(cs) < 0:
+        raise ValueError("col_steps must not be negative")
+    op = _op(operator)
+    bv = Vec(b)
+    yt = np.ascontiguousarray(y.T)  # C-order (m, ldy) == column-major (ldy, m)
+    a = np.ascontiguousarray(decomposition.alphas, dtype=np.float64).reshape(-1)
+    bb = np.ascontiguousarray(decomposition.betas, dtype=np.float64).reshape(-1)
+    x = bv.empty(m, op.nrows())
+    check(_lib.tpl_lanczos_pass_two_multi_cut(
+        op.handle, bv.ptr, bv.n, a.ctypes.data_as(POINTER(c_double)), a.shape[0],
+        bb.ctypes.data_as(POINTER(c_double)), bb.shape[0], int(decomposition.steps_taken),
+        float(decomposition.b_norm), yt.ctypes.data_as(POINTER(c_double)), ldy,
+        (ctypes.c_size_t * m)(*cs), m, Vec.ptr_of(x), bv.mem))
     return x.T
 
 

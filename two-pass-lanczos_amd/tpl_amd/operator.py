@@ -346,6 +346,21 @@ class HipCsrOp:
             on.ctypes.data_as(POINTER(ctypes.c_int32))))
         return y[:m].T, on[:m].astype(bool)
 
+    def ftk_inv_shifts_device(self, alphas, betas, sigmas):
+        """The device kernel of ``lanczos_two_pass_shifted_inv_tol`` alone, nothing eliminated
+        beforehand: (T_n + sigma_i I)^{-1} e_1 for every shift of ``sigmas`` -> Y of shape
+        (n, m), strides (1, n), unscaled; column i is bitwise ``ftk.inv`` on
+        ``(alphas + sigma_i, betas)``."""
+        a = np.ascontiguousarray(alphas, dtype=np.float64)
+        b = np.ascontiguousarray(betas, dtype=np.float64)
+        sg = np.ascontiguousarray(np.atleast_1d(np.asarray(sigmas, dtype=np.float64)).reshape(-1))
+        n, m = a.shape[0], sg.shape[0]
+        y = np.zeros((max(m, 1), n))
+        check(_lib.tpl_op_ftk_inv_shifts_device(
+            self._op, a.ctypes.data_as(POINTER(c_double)), n, b.ctypes.data_as(POINTER(c_double)),
+            sg.ctypes.data_as(POINTER(c_double)), m, y.ctypes.data_as(POINTER(c_double))))
+        return y[:m].T
+
     def ftk_exp_times_batch_device(self, alphas_list, betas_list, ts, ld=None):
         """The device kernel of ``lanczos_two_pass_batch_exp_times`` alone, on a group of nb
         (2 or 4) tridiagonals: ``alphas_list[c]`` (steps_c entries) and ``betas_list[c]``

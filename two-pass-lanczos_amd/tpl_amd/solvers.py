@@ -35,6 +35,10 @@ returns shape (n, m) with strides (1, n).
 solve that stops when the Lanczos residual estimate is <= ``tol``: bitwise
 ``lanczos_two_pass(operator, b, m*, "inv")`` for the first such step m* <= kmax.
 
+``lanczos_two_pass_shifted_inv_tol(operator, b, kmax, sigmas, tol)`` (no reference counterpart)
+is the same for (A + sigma_i I)^{-1} b at m shifts over the one Krylov space of A, every shift
+stopped at its own step m*_i. It returns shape (n, m) with strides (1, n).
+
 ``lanczos_two_pass_batch_exp_times(operator, B, k, ts)`` (no reference counterpart) is the same
 for the s columns of ``B`` in lock-step: exp(t_i A) b_c, every exp(t_i T_k) e_1 of a group of
 columns evaluated by one device launch. It returns shape (n, m, s) with strides (1, n, n m).
@@ -146,6 +150,39 @@ def lanczos_two_pass_inv_tol(operator, b, kmax: int, tol: float, return_info: bo
         return x
     return x, {"steps": int(steps.value), "converged": bool(conv.value),
                "residuals": res[: rlen.value].copy()}
+
+
+def lanczos_two_pass_shifted_inv_tol(operator, b, kmax: int, sigmas, tol: float,
+                                     return_info: bool = False):
+    """(A + sigma_i I)^{-1} b for the m shifts ``sigmas`` by ONE two-pass run on A, each shift
+    stopped at the first step m*_i whose relative Lanczos residual
+    (``ftk.inv_residuals(alphas + sigma_i, betas)``) is <= ``tol``, or at the steps pass one
+    took. Column i is bitwise ``algorithms.lanczos_pass_two`` on A's decomposition cut to m*_i
+    steps with y_i = ||b|| INV(alphas[:m*_i] + sigma_i, betas[:m*_i - 1]); it depends neither on
+    m nor on the other shifts. On one GPU within the device-inv bounds (``set_device_ftk``) the
+    whole call is one graph: pass one's elimination workgroup runs one lane per shift and the
+    stop is taken on the device when every shift has met the tolerance. Returns shape (n, m)
+    with strides (1, n); with ``return_info`` also a dict: ``steps`` ((m,) int array of m*_i),
+    ``converged`` ((m,) bool array) and ``residuals`` (a list of m numpy arrays: each history up
+    to the last entry formed, at least the first min(m*_i, steps taken by pass one - 1))."""
+    sg = np.ascontiguousarray(np.atleast_1d(np.asarray(sigmas, dtype=np.float64)).reshape(-1))
+    m = int(sg.shape[0])
+    operator = as_operator(operator)
+    bv = Vec(b)
+    x = bv.empty(max(m, 1), operator.nrows())  # C-order (m, n) == column-major (n, m)
+    kcap = max(int(kmax), 1)
+    res = np.zeros((max(m, 1), kcap), dtype=np.float64)  # column-major (kmax, m)
+    steps = (ctypes.c_size_t * max(m, 1))()
+    rlen = (ctypes.c_size_t * max(m, 1))()
+    conv = (ctypes.c_int32 * max(m, 1))()
+    check(_lib.tpl_lanczos_two_pass_shifted_inv_tol(
+        operator.handle, bv.ptr, bv.n, kmax, sg.ctypes.data_as(_lib.PD), m, float(tol),
+        Vec.ptr_of(x), bv.mem, steps, conv, res.ctypes.data_as(_lib.PD), rlen))
+    if not return_info:
+        return x.T
+    return x.T, {"steps": np.array(steps[:m], dtype=np.int64),
+                 "converged": np.array(conv[:m], dtype=bool),
+                 "residuals": [res[i, : rlen[i]].copy() for i in range(m)]}
 
 
 def lanczos_two_pass_batch(operator, B, k: int, f_tk_solver):
