@@ -471,6 +471,89 @@ tpl_status tpl_lanczos_pass_two_batch_multi(tpl_op_t op, const double* B, int64_
 tpl_status tpl_lanczos_two_pass_batch_exp_times(tpl_op_t op, const double* B, int64_t b_len,
                                                 size_t s, size_t k, const double* ts, size_t m,
                                                 double* x_out, int mem, int32_t* on_device);
+/* (A + sigma_i I)^{-1} b_c for the s columns of B and the m shifts sigmas[0..m) in one run,
+ * every (column, shift) stopped at the residual tolerance: the batch sibling of
+ * tpl_lanczos_two_pass_shifted_inv_tol. B is column-major n x s; x_out is column-major
+ * n x (s m), result (c, i) at column (c m + i), as tpl_lanczos_two_pass_batch_multi's; steps,
+ * converged and res_len hold s m entries at c m + i; res_out is column-major kmax x (s m).
+ * steps, converged, res_out and res_len may each be NULL.
+ * Definition, in bits: the outputs for (c, .) are what
+ * tpl_lanczos_two_pass_shifted_inv_tol(op, b_c, kmax, sigmas, m, tol) returns — x, steps,
+ * converged, the guaranteed prefix of each history (the first min(m*_{c,i}, steps_c - 1)
+ * entries) and the res_len rules. So result (c, i) is also the fixed-k single solve at
+ * k = m*_{c,i} with the shifted-inv closure, and depends neither on s, nor on m, nor on its
+ * position, nor on what the other columns hold (non-finite values included), nor on the
+ * long-row cache mask, nor on which path ran. A column that breaks down at step j_c keeps
+ * steps_c = j_c for all its shifts; the others run on to their own end.
+ * Grouping: the batch solve's rule, unchanged: four columns per group while four remain,
+ * then two, no group padded; a last single column runs tpl_lanczos_two_pass_shifted_inv_tol's
+ * body on that b, with that entry point's own routing.
+ * Host-composed path (mode 0 of tpl_op_set_device_ftk, TPL_NO_GRAPH=1, an eager operator,
+ * kmax past the line below; the oracle of the device path), per group: the lock-step pass one
+ * to kmax; per column ascending the zero-vector check, then per shift the history, the stop
+ * rule and y on the first m*_{c,i} rows, as the single call's host path; M_c = max_i m*_{c,i}
+ * becomes column c's device-held step count; ONE pass two of max_c M_c steps whose flush
+ * (k_bp2_xacc_cut) gives result (c, i) term t only where t < m*_{c,i}.
+ * Device path, on a single GPU with graphs in use — in mode 1 up to kmax = 1365 (the device
+ * inv's bound), in mode 2 (auto) up to kmax = 250, the largest measured kmax at which
+ * the graph was no slower than the host-composed path at every measured (s, m) (below) —
+ * one graph per group, cached per
+ * (kmax, group width, m) and replayed for any tolerance, shifts and B: the elimination
+ * workgroup of the batch pass one (k_bp1_axpy_stol) runs wave c for column c and lane i of it
+ * for shift i; when every lane of wave c has stopped, column c stops (it stores nothing from
+ * about two steps past M_c on) while the other columns run on, and once every column has
+ * stopped the remaining launches return at once; k_ftk_inv_shifts then solves every (c, i) on
+ * its own m*_{c,i} rows, one launch per column; the batch-multi pass two runs with the cut.
+ * tpl_op_flags bit 5 reads 1 afterwards if and only if every group of four or two ran as one
+ * graph (a call with s = 1 reports what the single-b call reports); bit 8 follows the
+ * TPL_LONG_CACHE_TWO_PASS_BATCH_MULTI bit, the remainder column included; bit 9 reads 0.
+ * Device memory: beyond the batch-multi solve's buffers the operator's first call adds a
+ * 1,024-byte table of cuts (4 x TPL_MULTI_MAX int32; tpl_lanczos_pass_two_batch_multi_cut adds
+ * the same) and, on the device path, exactly 8 (1 + m) + 4 (8 m (3 + 5 kcap) + 8 m) bytes
+ * (kcap: the batch buffers' step capacity, max(kmax, 16) on a first call); a remainder column
+ * adds what tpl_lanczos_two_pass_shifted_inv_tol adds.
+ * Errors, in this order and before any device work, each TPL_ERR_INVALID_ARGUMENT: NULL op, B,
+ * sigmas or x_out; s == 0 or s > TPL_BATCH_MAX; m == 0 or m > TPL_MULTI_MAX; tol NaN or
+ * negative (+inf is valid); a non-finite sigma_i. Then tpl_lanczos_two_pass_batch_multi's: a
+ * host-only plan is refused as by every solver, a partitioned operator is
+ * TPL_ERR_UNSUPPORTED, then b_len and kmax = 0; a zero column is the single solve's
+ * zero-vector InputError, for the first such column in ascending order. On an error x_out is
+ * unspecified. No live timing (tpl_op_pass_timing keeps its values).
+ * Measured on one MI355X (profiles/batch_shifted_inv_tol_timing.txt; 500k block
+ * with D, shifts between 1 and 100, medians): s = 4, m = 1, kmax = 500 at tol 1e-4 (the columns
+ * stop at 110 - 128) takes 20.3 ms as one graph and 21.7 ms composed on the host, against
+ * 24.8 ms for four tpl_lanczos_two_pass_shifted_inv_tol calls and 28.6 ms for
+ * tpl_lanczos_two_pass_batch_multi with inv_shift closures at k = 500; s = 4, m = 8 (one shift
+ * never stops: every pass runs to 500) 33.8, 33.5, 42.2 and 38.6 ms. The graph over the host
+ * path: 0.96 - 1.01 at kmax = 250, every difference within the repetitions' noise; at 500, 0.93
+ * - 0.95 where the four columns stop but 1.01 (+0.24 to +0.37 ms) where a shift never does; at
+ * 125 and 64, where nothing stops, 0.99 - 1.02 (+0.10 ms at most) — so auto mode's graph is up
+ * to 2 % slower than the host-composed path there, and mode 0 avoids that. At every measured
+ * shape either path is 0.78 - 0.95 of the s single-b calls. Where no column stops and m = 1
+ * (kmax = 64 and 125) the call is 5 - 11 % slower than tpl_lanczos_two_pass_batch_multi at the
+ * fixed k, which then runs the batch solve's pass two without flush launches; with m >= 4 or
+ * a stop it is 0.71 - 1.00 of it. */
+tpl_status tpl_lanczos_two_pass_batch_shifted_inv_tol(
+    tpl_op_t op, const double* B, int64_t b_len, size_t s, size_t kmax, const double* sigmas,
+    size_t m, double tol, double* x_out, int mem, size_t* steps, int32_t* converged,
+    double* res_out, size_t* res_len);
+/* The kmax up to which auto mode (tpl_op_set_device_ftk mode 2) runs a group of the call
+ * above as one graph. */
+size_t tpl_batch_shifted_inv_tol_auto_k(void);
+/* tpl_lanczos_pass_two_batch_multi with a cut per (column, function): col_steps holds s m
+ * entries, 1 <= col_steps[c m + i] <= steps[c] (steps[c] >= 1), and result (c, i) is bitwise
+ * tpl_lanczos_pass_two for b_c on column c's decomposition cut to col_steps[c m + i] steps with
+ * the first that many entries of y's column (c m + i); the entries past the cut are never
+ * used. The sibling of tpl_lanczos_pass_two_multi_cut, which a last single column runs.
+ * Checked before any device work, each TPL_ERR_INVALID_ARGUMENT: a NULL argument, s, m, then
+ * per column ascending steps[c] (>= 1, <= ld), its col_steps, b_norms[c] (the zero-vector
+ * InputError) and betas. */
+tpl_status tpl_lanczos_pass_two_batch_multi_cut(tpl_op_t op, const double* B, int64_t b_len,
+                                                size_t s, const double* alphas,
+                                                const double* betas, size_t ld,
+                                                const size_t* steps, const double* b_norms,
+                                                const double* y, const size_t* col_steps,
+                                                size_t m, double* x_out, int mem);
 
 /* Where tpl_lanczos_two_pass evaluates the built-in f(T_k): mode 0 = host (two graphs
  * around the host call), 1 = device (the whole solve one graph), 2 = auto (default).

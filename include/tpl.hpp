@@ -663,6 +663,35 @@ inline Mat lanczos_two_pass_batch_exp_times(const HipCsrOp& op, const Mat& B, si
       TPL_MEM_HOST, on_device ? on_device->data() : nullptr));
   return x;
 }
+// (A + sigma_i I)^{-1} b_c for the shifts `sigmas` and the s columns of B (n x s) by one run
+// (tpl_lanczos_two_pass_batch_shifted_inv_tol): per group of columns pass one on A in
+// lock-step, every (column, shift) stopped at its own step m*_{c,i}, one pass two cut per
+// result. Column (c m + i) of the n x (s m) result is bitwise column i of
+// lanczos_two_pass_shifted_inv_tol for B's column c. info, if given, holds per entry
+// (c m + i): m*_{c,i}, whether the tolerance was met, and the history up to the last entry
+// formed.
+inline Mat lanczos_two_pass_batch_shifted_inv_tol(const HipCsrOp& op, const Mat& B, size_t kmax,
+                                                  const std::vector<double>& sigmas, double tol,
+                                                  ShiftedInvTolInfo* info = nullptr) {
+  if (B.rows != op.ncols()) throw LanczosError::dimension_mismatch(op.ncols(), B.rows);
+  const size_t m = sigmas.size(), sm = B.cols * m, ldr = kmax ? kmax : 1;
+  Mat x(op.nrows(), sm);
+  std::vector<double> res(ldr * (sm ? sm : 1));
+  std::vector<size_t> steps(sm ? sm : 1), res_len(sm ? sm : 1);
+  std::vector<int32_t> converged(sm ? sm : 1);
+  detail::check(tpl_lanczos_two_pass_batch_shifted_inv_tol(
+      op.handle(), B.data.data(), (int64_t)B.rows, B.cols, kmax, sigmas.data(), m, tol,
+      x.data.data(), TPL_MEM_HOST, steps.data(), converged.data(), res.data(), res_len.data()));
+  if (info) {
+    *info = ShiftedInvTolInfo{};
+    for (size_t e = 0; e < sm; ++e) {
+      info->steps.push_back(steps[e]);
+      info->converged.push_back(converged[e] != 0);
+      info->residuals.emplace_back(res.begin() + e * ldr, res.begin() + e * ldr + res_len[e]);
+    }
+  }
+  return x;
+}
 }  // namespace solvers
 
 // ---- low-level API: src/algorithms/ -----------------------------------------------------

@@ -185,6 +185,18 @@ extern "C" {
                                         alphas: *const f64, betas: *const f64, ld: usize,
                                         steps: *const usize, b_norms: *const f64, y: *const f64,
                                         m: usize, x_out: *mut f64, mem: c_int) -> c_int;
+    fn tpl_lanczos_two_pass_batch_shifted_inv_tol(op: *mut TplOp, B: *const f64, b_len: i64,
+                                                  s: usize, kmax: usize, sigmas: *const f64,
+                                                  m: usize, tol: f64, x_out: *mut f64,
+                                                  mem: c_int, steps: *mut usize,
+                                                  converged: *mut i32, res_out: *mut f64,
+                                                  res_len: *mut usize) -> c_int;
+    fn tpl_lanczos_pass_two_batch_multi_cut(op: *mut TplOp, B: *const f64, b_len: i64, s: usize,
+                                            alphas: *const f64, betas: *const f64, ld: usize,
+                                            steps: *const usize, b_norms: *const f64,
+                                            y: *const f64, col_steps: *const usize, m: usize,
+                                            x_out: *mut f64, mem: c_int) -> c_int;
+    fn tpl_batch_shifted_inv_tol_auto_k() -> usize;
     fn tpl_copy_to_host(dst: *mut c_void, src_device: *const c_void, bytes: usize) -> c_int;
     fn tpl_op_nrows(op: *mut TplOp) -> i64;
     fn tpl_op_local_rows(op: *mut TplOp, rows: *mut i64) -> c_int;
@@ -1130,6 +1142,92 @@ where
             check(tpl_lanczos_two_pass_batch_multi(op.op, bv.as_ptr(), n as i64, s, k,
                                                    fns.as_ptr(), users.as_mut_ptr(), m,
                                                    x.as_mut_ptr(), TPL_MEM_HOST))?;
+        }
+        Ok(column_major(&x, op.n, s * m))
+    })?
+}
+
+/// (A + sigma_i I)^{-1} b_c for the shifts `sigmas` and the s columns of `b` (n x s) by ONE run
+/// (no reference counterpart): per group of columns pass one on A in lock-step, every
+/// (column, shift) stopped at the first step m*_{c,i} whose relative Lanczos residual is
+/// <= `tol`, one pass two cut per result. Column (c m + i) of the n x (s m) result is bitwise
+/// column i of `lanczos_two_pass_shifted_inv_tol` for `b`'s column c; the info's entries are
+/// in the same order.
+pub fn lanczos_two_pass_batch_shifted_inv_tol<O: HipOperand>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    kmax: usize,
+    sigmas: &[f64],
+    tol: f64,
+    stack: &mut MemStack,
+) -> Result<(Mat<f64>, ShiftedInvTolInfo), LanczosError> {
+    let _ = stack;
+    let (n, s) = (b.nrows(), b.ncols());
+    let bv: Vec<f64> = (0..n * s).map(|t| b[(t % n, t / n)]).collect();
+    let m = sigmas.len();
+    let sm = s * m;
+    let ldr = kmax.max(1);
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n * sm];
+        let mut res = vec![0.0; ldr * sm.max(1)];
+        let mut steps = vec![0usize; sm.max(1)];
+        let mut res_len = vec![0usize; sm.max(1)];
+        let mut converged = vec![0i32; sm.max(1)];
+        let _g = op.lock.lock().unwrap();
+        // SAFETY: b has n s entries, x n s m, res kmax s m; the other arrays hold s m entries.
+        unsafe {
+            check(tpl_lanczos_two_pass_batch_shifted_inv_tol(
+                op.op, bv.as_ptr(), n as i64, s, kmax, sigmas.as_ptr(), m, tol, x.as_mut_ptr(),
+                TPL_MEM_HOST, steps.as_mut_ptr(), converged.as_mut_ptr(), res.as_mut_ptr(),
+                res_len.as_mut_ptr()))?;
+        }
+        let residuals = (0..sm).map(|e| res[e * ldr..e * ldr + res_len[e]].to_vec()).collect();
+        steps.truncate(sm);
+        Ok((column_major(&x, op.n, sm),
+            ShiftedInvTolInfo { steps, converged: converged[..sm].iter().map(|&v| v != 0).collect(),
+                                residuals }))
+    })?
+}
+
+/// The kmax up to which auto mode runs a group of `lanczos_two_pass_batch_shifted_inv_tol` as
+/// one graph.
+pub fn batch_shifted_inv_tol_auto_k() -> usize {
+    // SAFETY: no arguments, no state.
+    unsafe { tpl_batch_shifted_inv_tol_auto_k() }
+}
+
+/// `tpl_lanczos_pass_two_batch_multi` with a cut per (column, coefficient vector)
+/// (`tpl_lanczos_pass_two_batch_multi_cut`): the decompositions as `lanczos_pass_one_batch`
+/// wrote them (leading dimension `ld`), `y` column-major ld x (s m), `col_steps[c m + i]` the
+/// steps result (c, i) takes (1 ..= steps[c]). Result (c, i) is bitwise `lanczos_pass_two` at
+/// that count.
+pub fn lanczos_pass_two_batch_multi_cut<O: HipOperand>(
+    operator: &O,
+    b: MatRef<'_, f64>,
+    alphas: &[f64],
+    betas: &[f64],
+    ld: usize,
+    steps: &[usize],
+    b_norms: &[f64],
+    y: &[f64],
+    col_steps: &[usize],
+) -> Result<Mat<f64>, LanczosError> {
+    let (n, s) = (b.nrows(), b.ncols());
+    let bv: Vec<f64> = (0..n * s).map(|t| b[(t % n, t / n)]).collect();
+    assert!(s > 0 && col_steps.len() % s == 0, "col_steps holds s m entries");
+    let m = col_steps.len() / s;
+    assert!(steps.len() == s && b_norms.len() == s, "one step count and one norm per column");
+    assert!(alphas.len() >= ld * s && betas.len() >= ld * s && y.len() >= ld * s * m,
+            "decomposition arrays hold fewer than ld entries per column");
+    operator.with_hip_op(|op| {
+        let mut x = vec![0.0; op.n * s * m];
+        let _g = op.lock.lock().unwrap();
+        // SAFETY: the lengths asserted above; x has n s m entries.
+        unsafe {
+            check(tpl_lanczos_pass_two_batch_multi_cut(
+                op.op, bv.as_ptr(), n as i64, s, alphas.as_ptr(), betas.as_ptr(), ld,
+                steps.as_ptr(), b_norms.as_ptr(), y.as_ptr(), col_steps.as_ptr(), m,
+                x.as_mut_ptr(), TPL_MEM_HOST))?;
         }
         Ok(column_major(&x, op.n, s * m))
     })?

@@ -55,6 +55,36 @@ hipError_t ftk_inv_shifts(const DevState& S, int k, const ShiftTol& t, double* Y
 hipError_t p2_xacc_cut(const CsrDev& A, const double* Y, int ldy, int j, int nflush,
                        const int32_t* cs, const double* vp, const double* vc, const double* vn,
                        double* X, int64_t ldx, int m, hipStream_t s);
+// ---- the same for a batch group (tpl_k_batch_stol.hip): every column of the group has a
+// ShiftTol block of its own; tol and sig are shared. t0 is column 0's view; column c's arrays
+// sit c dstride doubles (st, lu, res) and c istride int32 (hits, nres) further on.
+struct BatchShiftTol {
+  ShiftTol t0;
+  size_t dstride, istride;
+  ShiftTol col(int c) const {
+    ShiftTol v = t0;
+    v.st += (size_t)c * dstride;
+    v.lu += (size_t)c * dstride;
+    v.res += (size_t)c * dstride;
+    v.hits += (size_t)c * istride;
+    v.nres += (size_t)c * istride;
+    return v;
+  }
+};
+// bp1_axpy (tpl_batch.h) with the elimination workgroup of k_bp1_axpy_stol: wave c, lane i
+// eliminates column c's T_k + sig[i] I; column c stops when every shift of it has met the
+// tolerance, with M_c = max_i m*_{c,i} in its flag word 6. bp1_stol_fin: after the last step,
+// one wave per column settles steps_c and the history of a two-step pass.
+hipError_t bp1_axpy_stol(int nb, const CsrDev& A, const BatchDev& B, const double* W,
+                         const double* r_cur, double* r_next, int j, int k,
+                         const BatchShiftTol& t, hipStream_t s);
+hipError_t bp1_stol_fin(int nb, const BatchDev& B, const BatchShiftTol& t, hipStream_t s);
+// bp2_xacc (tpl_batch.h) with a cut per (function, column), read on the device
+// (k_bp2_xacc_cut): after step j, of the last nflush (1..3) terms, term t of result (f, c)
+// only where t < cs[c cld + f]; m <= kBatchMultiFuncs functions per launch
+hipError_t bp2_xacc_cut(int nb, const CsrDev& A, const BatchDev& B, const int32_t* cs, int cld,
+                        const double* Y, int j, int nflush, const double* vp, const double* vc,
+                        const double* vn, double* X, int64_t xstride, int m, hipStream_t s);
 hipError_t p2_tail(int64_t n, const DevState& S, double* x, double* const V[3], hipStream_t s);
 hipError_t permute(int64_t n, int cols, double* out, int64_t ldo, const double* in, int64_t ldi,
                    const int32_t* idx, hipStream_t s);

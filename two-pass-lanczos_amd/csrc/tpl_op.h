@@ -122,6 +122,15 @@ struct BatchBufs {
   double* d_ycache = nullptr;
   size_t yrows = 0;
   int32_t* d_ylrow = nullptr;
+  // The per-(column, shift) state of tpl_lanczos_two_pass_batch_shifted_inv_tol's device path
+  // (ensure_batch_stol), for kBatchNbMax columns, stol_m shifts and this kcap: one allocation
+  // {tol, sig[m]} | per column {st[3 m], lu[4 kcap m], res[kcap m]} doubles | per column
+  // {hits[m], nres[m]} int32, and the pinned mirror of flags | hits, nres | res of every
+  // column; nullptr until the first call that takes that path. They come and go with the
+  // batch buffers (free_batch)
+  double* d_stol = nullptr;
+  void* h_stol = nullptr;
+  size_t stol_m = 0;
   BatchDev S{};
 };
 
@@ -217,7 +226,12 @@ struct tpl_op_s {
   double* d_stol = nullptr;
   void* h_stol = nullptr;
   size_t stol_m = 0, stol_cap = 0;
-  tpl::BatchBufs bat;              // lock-step batch solves (ensure_batch)
+  // the cut table of a batch-multi pass two with a cut per (column, function)
+  // (ensure_batch_cut: kBatchNbMax * TPL_MULTI_MAX int32, entry c TPL_MULTI_MAX + f; uploaded
+  // by the host-composed paths, written by k_ftk_inv_shifts on the device path); nullptr until
+  // the first such call, never replaced
+  int32_t* d_bcut = nullptr;
+  tpl::BatchBufs bat;             // lock-step batch solves (ensure_batch)
   std::map<std::pair<int, size_t>, tpl::GraphExec> graphs;
   // device allocations of this operator (pointer -> bytes): tpl_op_device_bytes
   std::map<const void*, size_t> allocs;
@@ -356,6 +370,16 @@ void free_batch(tpl_op_s* op);
 // regrows the batch buffers frees them (free_batch). stage: also the host-side staging
 // block of the n x (nb m) result.
 void ensure_batch_multi(tpl_op_s* op, size_t m, bool stage);
+// The cut table of a batch-multi pass two (op->d_bcut: kBatchNbMax * TPL_MULTI_MAX int32,
+// 1,024 bytes), allocated on the first call that cuts a group's pass two per (column,
+// function), counted in device_bytes, freed with the operator.
+void ensure_batch_cut(tpl_op_s* op);
+// The per-(column, shift) state of tpl_lanczos_two_pass_batch_shifted_inv_tol's device path
+// (op->bat.d_stol, op->bat.h_stol) for m shifts and the batch buffers' current kcap
+// (ensure_batch first): 8 (1 + m) + kBatchNbMax (8 m (3 + 5 kcap) + 8 m) bytes, counted in
+// device_bytes. They grow with m; replacing them drops the cached graphs, which hold the
+// pointers (the first allocation drops nothing). -> the kernels' view for this call's m.
+launch::BatchShiftTol ensure_batch_stol(tpl_op_s* op, size_t m);
 double* ensure_view(tpl_op_s* op, size_t cols);
 // Per-step second-pass records of the selective re-orthogonalisation (slot j - 1: step j).
 int* reorth_records(const tpl_op_s* op);
@@ -432,6 +456,19 @@ void run_pass2_batch(tpl_op_s* op, size_t kmax, int nb);
 // device state holds them. All equal (the normal case): one graph per (kmax, nb, m);
 // otherwise the launch list depends on every steps_c and runs uncaptured.
 void run_pass2_batch_multi(tpl_op_s* op, const size_t* steps, int nb, size_t m);
+// The same with a cut per (column, function): result (f, c) takes the terms below
+// op->d_bcut[c TPL_MULTI_MAX + f] only (k_bp2_xacc_cut; 1 <= that count <= steps_c, the
+// device-held step count of column c), so it holds the bits of the single pass two at that
+// many steps. steps: the group's largest steps_c. One graph per (steps, nb, m): the counts
+// are device data.
+void run_pass2_batch_multi_cut(tpl_op_s* op, size_t steps, int nb, size_t m);
+// One group of the batch shifted inverse solve as one graph (ensure_batch, ensure_batch_multi,
+// ensure_batch_cut first; the group's b interleaved in op->bat.b; tolerance, shifts and
+// zeroed hit tables uploaded): pass one with k_bp1_axpy_stol, k_bp1_stol_fin,
+// k_ftk_inv_shifts per column into op->bat.d_my and op->d_bcut, the batch-multi pass two
+// with the cut. One graph per (kmax, nb, m).
+void run_two_pass_batch_shifted_inv_tol(tpl_op_s* op, size_t kmax, int nb,
+                                        const launch::BatchShiftTol& t);
 void run_two_pass_dev(tpl_op_s* op, size_t k, int f);
 // The one-graph inverse solve that stops at the tolerance in op->d_tol[0] (ensure_tol and
 // the upload of the tolerance and of the zeroed hit words first): one graph per kmax.

@@ -17,6 +17,7 @@ tpl_op_s::~tpl_op_s() {
   if (h_exp_back) hipHostFree(h_exp_back);
   if (h_tol) hipHostFree(h_tol);
   if (h_stol) hipHostFree(h_stol);
+  if (bat.h_stol) hipHostFree(bat.h_stol);
   if (h_expb_back) hipHostFree(h_expb_back);
   if (ev0) hipEventDestroy(ev0);
   if (ev1) hipEventDestroy(ev1);
@@ -482,6 +483,8 @@ void free_batch(tpl_op_s* op) {
   dev_free(op, b.d_stage);
   dev_free(op, b.d_mx), dev_free(op, b.d_my), dev_free(op, b.d_mstage);
   dev_free(op, b.d_ycache);
+  dev_free(op, b.d_stol);
+  if (b.h_stol) hipHostFree(b.h_stol);
   b = BatchBufs{};
 }
 namespace {
@@ -541,6 +544,50 @@ void ensure_batch_multi(tpl_op_s* op, size_t m, bool stage) {
               std::max<size_t>((size_t)op->part.n, 1) * w * cols * sizeof(double));
     b.mstage_cols = cols;
   }
+}
+void ensure_batch_cut(tpl_op_s* op) {
+  if (op->d_bcut) return;
+  constexpr size_t bytes = (size_t)kBatchNbMax * TPL_MULTI_MAX * sizeof(int32_t);
+  dev_alloc(op, &op->d_bcut, bytes);
+  HIPCHK(hipMemset(op->d_bcut, 0, bytes));
+}
+launch::BatchShiftTol ensure_batch_stol(tpl_op_s* op, size_t m) {
+  BatchBufs& b = op->bat;
+  if (b.nb == 0 || m == 0)
+    fail(TPL_ERR_INVALID_ARGUMENT, "ensure_batch_stol: no batch buffers to size by");
+  const size_t kc = b.kcap, w = (size_t)kBatchNbMax;
+  if (!b.d_stol || b.stol_m < m) {
+    const size_t mc = std::max(m, b.stol_m);
+    if (b.d_stol) drop_graphs(op);  // they hold the pointers being replaced
+    dev_free(op, b.d_stol);
+    if (b.h_stol) hipHostFree(b.h_stol);
+    b.h_stol = nullptr;
+    b.stol_m = 0;
+    const size_t doubles = 1 + mc + w * mc * (3 + 5 * kc);
+    const size_t bytes = doubles * sizeof(double) + w * 2 * mc * sizeof(int32_t);
+    dev_alloc(op, &b.d_stol, bytes);
+    HIPCHK(hipMemset(b.d_stol, 0, bytes));
+    HIPCHK(hipHostMalloc(&b.h_stol,
+                         w * (kFlagBytes + 2 * mc * sizeof(int32_t) + kc * mc * sizeof(double)),
+                         hipHostMallocDefault));
+    b.stol_m = mc;
+  }
+  // the arrays are laid out for the capacity; their inner stride is this call's m
+  const size_t mc = b.stol_m;
+  launch::BatchShiftTol t{};
+  double* p = b.d_stol;
+  t.t0.tol = p;
+  t.t0.sig = p + 1;
+  t.t0.st = p + 1 + mc;
+  t.t0.lu = t.t0.st + 3 * mc;
+  t.t0.res = t.t0.lu + 4 * kc * mc;
+  t.dstride = mc * (3 + 5 * kc);
+  t.t0.hits = reinterpret_cast<int32_t*>(p + 1 + mc + w * t.dstride);
+  t.t0.nres = t.t0.hits + mc;
+  t.istride = 2 * mc;
+  t.t0.m = (int32_t)m;
+  t.t0.kcap = (int32_t)kc;
+  return t;
 }
 // Freed before they grow, as the basis is. State layout, per group: [flags: 8 int32 per
 // column] [norms nb (kc + 1)] [alphas nb kc] [betas nb kc] [y nb kc] | 64-B aligned:

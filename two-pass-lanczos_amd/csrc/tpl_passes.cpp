@@ -30,6 +30,10 @@ enum GraphKind {
                       // per (steps, m) (the columns' step counts are device data)
   kGTwoPassShiftedInvTol,  // one-graph shifted inverse solve that stops each shift at a
                       // tolerance: one graph per (kmax, m) (tolerance and shifts: device data)
+  kGPass2BatchMultiCut,    // pass two of a batch-multi group with a cut per (column,
+                      // function): one graph per (steps, NB, m) (the counts are device data)
+  kGTwoPassBatchShiftedInvTol,  // one group of the batch shifted inverse solve that stops
+                      // every (column, shift) at a tolerance: one graph per (kmax, NB, m)
   kGLongCache = 64,   // + this: the sequence stores / reads the long-row cache (a two-pass
                       // solve with the cache on for it; other kernels, other graphs)
   kGFusedP2 = 128,    // + this: pass two is the fused one (k_p2_hub, k_p2_rows) in place of
@@ -506,6 +510,89 @@ void run_pass2_batch_multi(tpl_op_s* op, const size_t* steps, int nb, size_t m) 
   run_graph(op, kGPass2BatchMulti + batch_graph_cache_kind(op),
             (kmax * 8 + (size_t)nb) * (TPL_MULTI_MAX + 1) + m,
             [&] { enqueue_pass2_batch_multi(op, steps, nb, m); });
+}
+
+// The same with a cut per (column, function) (tpl_lanczos_pass_two_batch_multi_cut and the
+// batch shifted inverse solve): k_bp2_xacc_cut in place of k_bp2_xacc, the counts in
+// op->d_bcut. The step launches run for `steps` (the group's largest steps_c on the
+// host-composed paths, the count asked for in the one-graph solve), each column active below
+// its device-held steps_c (bp2_coefs0), and x is flushed by the single schedule for `steps`
+// (p2_flush: multiples of 3 and once after the last launch); the cut covers every column's
+// and every function's ragged end. The terms a result gets, and their order, are the same
+// whatever `steps` is.
+static void enqueue_pass2_batch_multi_cut(tpl_op_s* op, size_t steps, int nb, size_t m) {
+  const CsrDev A = csr_dev(op);
+  BatchBufs& bb = op->bat;
+  const BatchDev& S = bb.S;
+  const int64_t xs = op->ld * nb;  // one function's group vector
+  HIPCHK(launch::bp2_minit(nb, A, S, bb.d_my, (int)m, bb.b, bb.R[1], bb.d_mx, xs, op->stream));
+  HIPCHK(launch::bp2_coefs0(nb, S, (int)steps, op->stream));
+  for (int j = 1; j < (int)steps; ++j) {
+    double *vp = bb.R[(j + 2) % 3], *vc = bb.R[j % 3], *vn = bb.R[(j + 1) % 3];
+    launch_bp2_step(op, A, nb, j);
+    const int nflush = p2_flush(j, (int)steps - 1);
+    if (!nflush) continue;
+    for (size_t f0 = 0; f0 < m; f0 += kBatchMultiFuncs)
+      HIPCHK(launch::bp2_xacc_cut(nb, A, S, op->d_bcut + f0, TPL_MULTI_MAX,
+                                  bb.d_my + f0 * (size_t)nb * bb.kcap, j, nflush, vp, vc, vn,
+                                  bb.d_mx + f0 * (size_t)xs, xs,
+                                  (int)std::min<size_t>(kBatchMultiFuncs, m - f0), op->stream));
+  }
+}
+static void check_batch_multi_cut(const tpl_op_s* op, size_t steps, int nb, size_t m) {
+  check_batch(op, steps, nb);
+  if (m == 0 || m > op->bat.mcols || m > TPL_MULTI_MAX || !op->d_bcut)
+    fail(TPL_ERR_INVALID_ARGUMENT, "batch-multi group: buffers smaller than the request");
+}
+void run_pass2_batch_multi_cut(tpl_op_s* op, size_t steps, int nb, size_t m) {
+  check_batch_multi_cut(op, steps, nb, m);
+  op->last_long_cache = steps >= 2 && batch_cache_steps(op) > 0;
+  run_graph(op, kGPass2BatchMultiCut + batch_graph_cache_kind(op),
+            (steps * 8 + (size_t)nb) * (TPL_MULTI_MAX + 1) + m,
+            [&] { enqueue_pass2_batch_multi_cut(op, steps, nb, m); });
+}
+
+// One group of the batch shifted inverse solve as one graph: run_pass1_batch's sequence with
+// k_bp1_axpy_stol in place of k_bp1_axpy, k_bp1_stol_fin, every (T_c + sigma_i I)^{-1} e_1 at
+// its own m*_{c,i} by k_ftk_inv_shifts — one launch per column, in series, on column c's view
+// of the group state, into the batch-multi coefficient layout and column c's row of the cut
+// table — then the batch-multi pass two with the cut. A column whose shifts have all met the
+// tolerance stores nothing more; once every column has stopped the later launches of pass one
+// return at their stop test, the step launches of pass two past every M_c are inactive and
+// the flush launches past every cut return at once.
+void run_two_pass_batch_shifted_inv_tol(tpl_op_s* op, size_t kmax, int nb,
+                                        const launch::BatchShiftTol& t) {
+  const size_t m = (size_t)t.t0.m;
+  check_batch_multi_cut(op, kmax, nb, m);
+  const int ck = batch_graph_cache_kind(op);
+  op->last_long_cache = kmax >= 2 && ck != 0;
+  run_graph(op, kGTwoPassBatchShiftedInvTol + ck,
+            (kmax * 8 + (size_t)nb) * (TPL_MULTI_MAX + 1) + m, [&] {
+    const CsrDev A = csr_dev(op);
+    BatchBufs& bb = op->bat;
+    const BatchDev& S = bb.S;
+    HIPCHK(launch::bp1_init(nb, A, S, bb.b, op->stream));
+    auto r_of = [&](int j) { return j == 1 ? bb.b : bb.R[j % 3]; };
+    for (int j = 1; j <= (int)kmax; ++j) {
+      HIPCHK(launch::bp1_spmv(nb, A, S, r_of(j), j >= 2 ? r_of(j - 1) : nullptr, bb.W, j,
+                              batch_cache_row(op, j, nb), op->stream));
+      HIPCHK(launch::bp1_axpy_stol(nb, A, S, bb.W, r_of(j), bb.R[(j + 1) % 3], j, (int)kmax, t,
+                                   op->stream));
+    }
+    HIPCHK(launch::bp1_stol_fin(nb, S, t, op->stream));
+    for (int c = 0; c < nb; ++c) {
+      DevState Sc{};  // column c's part of the group state, as k_ftk_inv_shifts reads it
+      Sc.flags = S.flags + 8 * c;
+      Sc.norms = S.norms + (size_t)c * (S.kcap + 1);
+      Sc.alphas = S.alphas + (size_t)c * S.kcap;
+      Sc.betas = S.betas + (size_t)c * S.kcap;
+      Sc.kcap = S.kcap;
+      HIPCHK(launch::ftk_inv_shifts(Sc, (int)kmax, t.col(c), bb.d_my + (size_t)c * bb.kcap,
+                                    nb * (int)bb.kcap, op->d_bcut + (size_t)c * TPL_MULTI_MAX, 1,
+                                    op->stream));
+    }
+    enqueue_pass2_batch_multi_cut(op, kmax, nb, m);
+  });
 }
 
 // Copy flags | norms[0] | alphas | betas back (one D2H), synchronise.

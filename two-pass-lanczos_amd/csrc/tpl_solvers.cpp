@@ -729,6 +729,109 @@ bool shifted_on_device(const tpl_op_s* op, size_t kmax) {
   return device_f(op, &tpl_ftk_inv, kmax) == kDevInv &&
          (op->device_ftk == 1 || kmax <= kShiftedAutoK) && use_graphs() && !op->eager;
 }
+// tpl_lanczos_two_pass_shifted_inv_tol after its argument checks, inside the caller's
+// LongCacheScope (the batch solve runs its remainder column through it).
+void shifted_inv_tol_one(tpl_op_s* op, const double* b, size_t kmax, const double* sigmas,
+                         size_t m, double tol, double* x_out, int mem, size_t* steps,
+                         int32_t* converged, double* res_out, size_t* res_len) {
+  auto report = [&](size_t i, size_t ms, bool hit, size_t n_res) {
+    if (steps) steps[i] = ms;
+    if (converged) converged[i] = hit ? 1 : 0;
+    if (res_len) res_len[i] = res_out ? n_res : 0;
+  };
+  ensure_state(op, kmax);
+  ensure_multi(op, m);
+  ensure_col_steps(op);
+  if (shifted_on_device(op, kmax)) {
+    // one graph: pass one with a lane per shift, every y_i on its own m*_i rows, pass two
+    const launch::ShiftTol t = ensure_stol(op, m);
+    upload_vec(op, op->b, b, mem);
+    const int32_t zero[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(op->st.S.flags + 6, zero, sizeof(zero), hipMemcpyHostToDevice,
+                          op->stream));
+    HIPCHK(hipMemsetAsync(t.hits, 0, 2 * op->stol_m * sizeof(int32_t), op->stream));
+    HIPCHK(hipMemcpyAsync(op->d_stol, &tol, sizeof(double), hipMemcpyHostToDevice, op->stream));
+    HIPCHK(hipMemcpyAsync(op->d_stol + 1, sigmas, m * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+    run_two_pass_shifted_inv_tol(op, kmax, t);
+    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+    char* h = (char*)op->h_stol;
+    int32_t* h_hits = (int32_t*)(h + kFlagBytes);
+    double* h_res = (double*)(h + kFlagBytes + 2 * op->stol_m * sizeof(int32_t));
+    HIPCHK(hipMemcpyAsync(h, op->st.d_state, kFlagBytes, hipMemcpyDeviceToHost, op->stream));
+    HIPCHK(hipMemcpyAsync(h_hits, t.hits, 2 * op->stol_m * sizeof(int32_t),
+                          hipMemcpyDeviceToHost, op->stream));
+    if (res_out && kmax > 1)
+      HIPCHK(hipMemcpyAsync(h_res, t.res, (kmax - 1) * m * sizeof(double),
+                            hipMemcpyDeviceToHost, op->stream));
+    sync_checked(op);
+    int32_t flags[kFlagBytes / 4];
+    std::memcpy(flags, h, kFlagBytes);
+    op->last_one_graph = true;
+    if (flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+    if (flags[2] == 0) {
+      zero_out_cols(op, x_out, m, mem);
+      for (size_t i = 0; i < m; ++i) report(i, 0, false, 0);
+      return;
+    }
+    const int32_t* h_nres = h_hits + op->stol_m;
+    for (size_t i = 0; i < m; ++i) {
+      const size_t formed = std::min<size_t>((size_t)h_nres[i], kmax - 1);
+      if (res_out)
+        for (size_t r = 0; r < formed; ++r) res_out[i * kmax + r] = h_res[r * m + i];
+      report(i, h_hits[i] ? (size_t)h_hits[i] : (size_t)flags[2], h_hits[i] != 0, formed);
+    }
+    return;
+  }
+  // composed on the host (the oracle of the device path): pass one to kmax, then per shift
+  // the history, the rule and y on the first m*_i rows, one pass two of M = max m*_i steps
+  op->last_one_graph = false;
+  run_pass_one(op, b, kmax, mem, false, false);
+  const HostDecomp d = fetch_decomp(op);
+  if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+  if (d.steps == 0) {
+    zero_out_cols(op, x_out, m, mem);
+    for (size_t i = 0; i < m; ++i) report(i, 0, false, 0);
+    return;
+  }
+  std::vector<double> Y(m * d.steps, 0.0);
+  int32_t cs[TPL_MULTI_MAX];
+  size_t M = 0;
+  for (size_t i = 0; i < m; ++i) {
+    const ShiftedCol c = shifted_col(d, sigmas[i], tol);
+    std::copy(c.y.begin(), c.y.end(), Y.begin() + i * d.steps);
+    cs[i] = (int32_t)c.steps;
+    M = std::max(M, c.steps);
+    if (res_out) std::copy(c.res.begin(), c.res.end(), res_out + i * kmax);
+    report(i, c.steps, c.converged, c.res.size());
+  }
+  upload_y(op, Y.data(), d.steps, M, m);
+  upload_col_steps(op, cs, m);
+  run_pass2_multi_cut(op, M, m);
+  download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+  sync_checked(op);
+}
+// tpl_lanczos_pass_two_multi_cut after its argument checks: the decomposition, the
+// coefficient columns and the cuts cs[0..m) to the device, the pass, the result out.
+void pass_two_multi_cut_run(tpl_op_s* op, const double* b, const double* alphas,
+                            const double* betas, size_t steps, double b_norm, const double* y,
+                            size_t ldy, const int32_t* cs, size_t m, double* x_out, int mem) {
+  ensure_state(op, steps);
+  ensure_multi(op, m);
+  const DevState& S = op->st.S;
+  HIPCHK(hipMemcpyAsync(S.norms, &b_norm, sizeof(double), hipMemcpyHostToDevice, op->stream));
+  HIPCHK(hipMemcpyAsync(S.alphas, alphas, steps * sizeof(double), hipMemcpyHostToDevice,
+                        op->stream));
+  if (steps > 1)
+    HIPCHK(hipMemcpyAsync(S.betas, betas, (steps - 1) * sizeof(double), hipMemcpyHostToDevice,
+                          op->stream));
+  upload_y(op, y, ldy, steps, m);
+  upload_col_steps(op, cs, m);
+  upload_vec(op, op->b, b, mem);
+  run_pass2_multi_cut(op, steps, m);
+  download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
+  sync_checked(op);
+}
 } // namespace
 
 extern "C" {
@@ -752,82 +855,8 @@ tpl_status tpl_lanczos_two_pass_shifted_inv_tol(tpl_op_t op, const double* b, in
     check_k(kmax);
     const TimingOff untimed(op);
     const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS_MULTI);
-    auto report = [&](size_t i, size_t ms, bool hit, size_t n_res) {
-      if (steps) steps[i] = ms;
-      if (converged) converged[i] = hit ? 1 : 0;
-      if (res_len) res_len[i] = res_out ? n_res : 0;
-    };
-    ensure_state(op, kmax);
-    ensure_multi(op, m);
-    ensure_col_steps(op);
-    if (shifted_on_device(op, kmax)) {
-      // one graph: pass one with a lane per shift, every y_i on its own m*_i rows, pass two
-      const launch::ShiftTol t = ensure_stol(op, m);
-      upload_vec(op, op->b, b, mem);
-      const int32_t zero[2] = {0, 0};
-      HIPCHK(hipMemcpyAsync(op->st.S.flags + 6, zero, sizeof(zero), hipMemcpyHostToDevice,
-                            op->stream));
-      HIPCHK(hipMemsetAsync(t.hits, 0, 2 * op->stol_m * sizeof(int32_t), op->stream));
-      HIPCHK(hipMemcpyAsync(op->d_stol, &tol, sizeof(double), hipMemcpyHostToDevice, op->stream));
-      HIPCHK(hipMemcpyAsync(op->d_stol + 1, sigmas, m * sizeof(double), hipMemcpyHostToDevice,
-                            op->stream));
-      run_two_pass_shifted_inv_tol(op, kmax, t);
-      download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
-      char* h = (char*)op->h_stol;
-      int32_t* h_hits = (int32_t*)(h + kFlagBytes);
-      double* h_res = (double*)(h + kFlagBytes + 2 * op->stol_m * sizeof(int32_t));
-      HIPCHK(hipMemcpyAsync(h, op->st.d_state, kFlagBytes, hipMemcpyDeviceToHost, op->stream));
-      HIPCHK(hipMemcpyAsync(h_hits, t.hits, 2 * op->stol_m * sizeof(int32_t),
-                            hipMemcpyDeviceToHost, op->stream));
-      if (res_out && kmax > 1)
-        HIPCHK(hipMemcpyAsync(h_res, t.res, (kmax - 1) * m * sizeof(double),
-                              hipMemcpyDeviceToHost, op->stream));
-      sync_checked(op);
-      int32_t flags[kFlagBytes / 4];
-      std::memcpy(flags, h, kFlagBytes);
-      op->last_one_graph = true;
-      if (flags[1]) fail_input("Input vector `b` must not be a zero vector.");
-      if (flags[2] == 0) {
-        zero_out_cols(op, x_out, m, mem);
-        for (size_t i = 0; i < m; ++i) report(i, 0, false, 0);
-        return;
-      }
-      const int32_t* h_nres = h_hits + op->stol_m;
-      for (size_t i = 0; i < m; ++i) {
-        const size_t formed = std::min<size_t>((size_t)h_nres[i], kmax - 1);
-        if (res_out)
-          for (size_t r = 0; r < formed; ++r) res_out[i * kmax + r] = h_res[r * m + i];
-        report(i, h_hits[i] ? (size_t)h_hits[i] : (size_t)flags[2], h_hits[i] != 0, formed);
-      }
-      return;
-    }
-    // composed on the host (the oracle of the device path): pass one to kmax, then per shift
-    // the history, the rule and y on the first m*_i rows, one pass two of M = max m*_i steps
-    op->last_one_graph = false;
-    run_pass_one(op, b, kmax, mem, false, false);
-    const HostDecomp d = fetch_decomp(op);
-    if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
-    if (d.steps == 0) {
-      zero_out_cols(op, x_out, m, mem);
-      for (size_t i = 0; i < m; ++i) report(i, 0, false, 0);
-      return;
-    }
-    std::vector<double> Y(m * d.steps, 0.0);
-    int32_t cs[TPL_MULTI_MAX];
-    size_t M = 0;
-    for (size_t i = 0; i < m; ++i) {
-      const ShiftedCol c = shifted_col(d, sigmas[i], tol);
-      std::copy(c.y.begin(), c.y.end(), Y.begin() + i * d.steps);
-      cs[i] = (int32_t)c.steps;
-      M = std::max(M, c.steps);
-      if (res_out) std::copy(c.res.begin(), c.res.end(), res_out + i * kmax);
-      report(i, c.steps, c.converged, c.res.size());
-    }
-    upload_y(op, Y.data(), d.steps, M, m);
-    upload_col_steps(op, cs, m);
-    run_pass2_multi_cut(op, M, m);
-    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
-    sync_checked(op);
+    shifted_inv_tol_one(op, b, kmax, sigmas, m, tol, x_out, mem, steps, converged, res_out,
+                        res_len);
   });
 }
 
@@ -852,21 +881,7 @@ tpl_status tpl_lanczos_pass_two_multi_cut(tpl_op_t op, const double* b, int64_t 
       fail_input("The initial vector `b` must not be a zero vector.");
     if (n_alphas < steps || n_betas + 1 < steps || !alphas || (steps > 1 && !betas))
       fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
-    ensure_state(op, steps);
-    ensure_multi(op, m);
-    const DevState& S = op->st.S;
-    HIPCHK(hipMemcpyAsync(S.norms, &b_norm, sizeof(double), hipMemcpyHostToDevice, op->stream));
-    HIPCHK(hipMemcpyAsync(S.alphas, alphas, steps * sizeof(double), hipMemcpyHostToDevice,
-                          op->stream));
-    if (steps > 1)
-      HIPCHK(hipMemcpyAsync(S.betas, betas, (steps - 1) * sizeof(double), hipMemcpyHostToDevice,
-                            op->stream));
-    upload_y(op, y, ldy, steps, m);
-    upload_col_steps(op, cs, m);
-    upload_vec(op, op->b, b, mem);
-    run_pass2_multi_cut(op, steps, m);
-    download_cols(op, x_out, op->d_X, op->ld, (int64_t)m, mem);
-    sync_checked(op);
+    pass_two_multi_cut_run(op, b, alphas, betas, steps, b_norm, y, ldy, cs, m, x_out, mem);
   });
 }
 
@@ -1478,6 +1493,255 @@ tpl_status tpl_op_ftk_exp_times_batch_device(tpl_op_t op, const double* alphas,
                           hipMemcpyDeviceToHost, op->stream));
     sync_checked(op);
     for (size_t e = 0; e < nb * m; ++e) on_device[e] = op->h_expb_back[e] ? 0 : 1;
+  });
+}
+
+} // extern "C"
+
+// ---- (A + sigma_i I)^{-1} b_c for s right-hand sides, every (c, i) stopped at the tolerance
+namespace {
+// Auto mode takes the one-graph path for a group up to this kmax: the largest measured kmax at
+// which the graph was no slower than the host-composed path at every measured (s, m), beyond
+// the repetitions' noise (scripts/batch_shifted_inv_tol_timing.py's rule, in both of its passes:
+// profiles/batch_shifted_inv_tol_timing.txt). 500k block with D, shifts 1 .. 100,
+// (s, m) = (2, 1), (4, 1), (4, 4), (4, 8), tol 1e-4 and 1e-8, graph over host path: 0.96 - 1.01
+// at kmax = 250, every difference within the noise. At 500 it is 0.93 - 0.95 where the four
+// columns stop (a lock-step step of four columns is worth far more than the 3.5 us an empty
+// launch costs, unlike the single solve's: kShiftedAutoK) but 1.01 where a shift never stops
+// (+0.24 to +0.37 ms: the nb k_ftk_inv_shifts launches in series, 85 us of chain each at 500
+// rows), and the routing cannot know which it will be. Below the line nothing stops and the
+// graph is 0.99 - 1.02 of the host path at kmax = 125 and 64 (+0.10 ms at most): the line's
+// cost. Against s single-b calls either path is 0.78 - 0.95 at every measured shape. Mode 1
+// takes the graph up to the device inv's bound.
+constexpr size_t kBatchShiftedAutoK = 250;
+// A group of four or two runs as one graph where the single shifted solve may (the device
+// inv's bounds, graphs in use), within the line above in auto mode.
+bool batch_shifted_on_device(const tpl_op_s* op, size_t kmax) {
+  return device_f(op, &tpl_ftk_inv, kmax) == kDevInv &&
+         (op->device_ftk == 1 || kmax <= kBatchShiftedAutoK) && use_graphs() && !op->eager;
+}
+// Column c's device-held step count (its flag word 2) := v, from a host word that lives
+// until the next synchronisation.
+void upload_col_count(tpl_op_s* op, int c, const int32_t* v) {
+  HIPCHK(hipMemcpyAsync(op->bat.S.flags + 8 * c + 2, v, sizeof(int32_t), hipMemcpyHostToDevice,
+                        op->stream));
+}
+} // namespace
+
+extern "C" {
+
+size_t tpl_batch_shifted_inv_tol_auto_k(void) { return kBatchShiftedAutoK; }
+
+tpl_status tpl_lanczos_two_pass_batch_shifted_inv_tol(
+    tpl_op_t op, const double* B, int64_t b_len, size_t s, size_t kmax, const double* sigmas,
+    size_t m, double tol, double* x_out, int mem, size_t* steps, int32_t* converged,
+    double* res_out, size_t* res_len) {
+  return guarded([&] {
+    if (!op || !B || !sigmas || !x_out) fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (s == 0 || s > (size_t)TPL_BATCH_MAX)
+      fail(TPL_ERR_INVALID_ARGUMENT, "s must be between 1 and TPL_BATCH_MAX");
+    if (m == 0 || m > (size_t)TPL_MULTI_MAX)
+      fail(TPL_ERR_INVALID_ARGUMENT, "m must be between 1 and TPL_MULTI_MAX");
+    if (!(tol >= 0.0)) fail(TPL_ERR_INVALID_ARGUMENT, "tol must be a number >= 0");
+    for (size_t i = 0; i < m; ++i)
+      if (!std::isfinite(sigmas[i]))
+        fail(TPL_ERR_INVALID_ARGUMENT, "every shift sigma_i must be finite");
+    set_device(op);
+    if (op->dist) fail(TPL_ERR_UNSUPPORTED, "batch-multi solve of a partitioned operator");
+    check_b(op, B, b_len);
+    check_k(kmax);
+    const TimingOff untimed(op);
+    const LongCacheScope cache(op, TPL_LONG_CACHE_TWO_PASS_BATCH_MULTI);
+    const size_t n = (size_t)op->part.n;
+    // result (c, i): entry e = c m + i of every output
+    auto report = [&](size_t e, size_t ms, bool hit, size_t n_res) {
+      if (steps) steps[e] = ms;
+      if (converged) converged[e] = hit ? 1 : 0;
+      if (res_len) res_len[e] = res_out ? n_res : 0;
+    };
+    const bool dev = batch_shifted_on_device(op, kmax);
+    bool groups_one_graph = true, any_group = false;
+    for (size_t c0 = 0; c0 < s;) {
+      const int nb = n == 0 ? 1 : group_width(s - c0);
+      if (nb == 1) {  // the single-b solve of that column, with its own routing
+        auto at = [&](auto* p) { return p ? p + c0 * m : nullptr; };
+        shifted_inv_tol_one(op, B + c0 * n, kmax, sigmas, m, tol, x_out + c0 * m * n, mem,
+                            at(steps), at(converged), res_out ? res_out + c0 * m * kmax : nullptr,
+                            at(res_len));
+        ++c0;
+        continue;
+      }
+      any_group = true;
+      ensure_batch(op, nb, kmax);
+      ensure_batch_multi(op, m, mem != TPL_MEM_DEVICE);
+      ensure_batch_cut(op);
+      BatchBufs& bb = op->bat;
+      if (dev) {
+        // one graph: pass one with a lane per (column, shift), every y_{c,i} on its own
+        // m*_{c,i} rows, the cut pass two
+        const launch::BatchShiftTol t = ensure_batch_stol(op, m);
+        const size_t mc = bb.stol_m, kc = bb.kcap, w = (size_t)kBatchNbMax;
+        upload_group(op, B + c0 * n, nb, mem);
+        HIPCHK(hipMemsetAsync(t.t0.hits, 0, w * 2 * mc * sizeof(int32_t), op->stream));
+        HIPCHK(hipMemcpyAsync(bb.d_stol, &tol, sizeof(double), hipMemcpyHostToDevice, op->stream));
+        HIPCHK(hipMemcpyAsync(bb.d_stol + 1, sigmas, m * sizeof(double), hipMemcpyHostToDevice,
+                              op->stream));
+        run_two_pass_batch_shifted_inv_tol(op, kmax, nb, t);
+        download_group_multi(op, x_out + c0 * m * n, nb, m, mem);
+        char* h = (char*)bb.h_stol;
+        int32_t* h_flags = (int32_t*)h;
+        int32_t* h_ints = (int32_t*)(h + w * kFlagBytes);
+        double* h_res = (double*)(h + w * kFlagBytes + w * 2 * mc * sizeof(int32_t));
+        HIPCHK(hipMemcpyAsync(h_flags, bb.S.flags, (size_t)nb * kFlagBytes, hipMemcpyDeviceToHost,
+                              op->stream));
+        HIPCHK(hipMemcpyAsync(h_ints, t.t0.hits, w * 2 * mc * sizeof(int32_t),
+                              hipMemcpyDeviceToHost, op->stream));
+        if (res_out && kmax > 1)
+          for (int c = 0; c < nb; ++c)
+            HIPCHK(hipMemcpyAsync(h_res + (size_t)c * kc * mc, t.col(c).res,
+                                  (kmax - 1) * m * sizeof(double), hipMemcpyDeviceToHost,
+                                  op->stream));
+        sync_checked(op);
+        for (int c = 0; c < nb; ++c) {
+          const int32_t* fl = h_flags + 8 * c;
+          if (fl[1]) fail_input("Input vector `b` must not be a zero vector.");
+          const int32_t* hits = h_ints + (size_t)c * 2 * mc;
+          const int32_t* nres = hits + mc;
+          const double* res = h_res + (size_t)c * kc * mc;
+          for (size_t i = 0; i < m; ++i) {
+            const size_t e = (c0 + (size_t)c) * m + i;
+            if (fl[2] == 0) {
+              report(e, 0, false, 0);
+              continue;
+            }
+            const size_t formed = std::min<size_t>((size_t)nres[i], kmax - 1);
+            if (res_out)
+              for (size_t r = 0; r < formed; ++r) res_out[e * kmax + r] = res[r * m + i];
+            report(e, hits[i] ? (size_t)hits[i] : (size_t)fl[2], hits[i] != 0, formed);
+          }
+        }
+        c0 += (size_t)nb;
+        continue;
+      }
+      // composed on the host (the oracle of the device path): the group's pass one to kmax,
+      // then per column in order the zero check and per shift the history, the rule and y on
+      // the first m*_{c,i} rows; M_c = max_i m*_{c,i} becomes column c's device-held step
+      // count, and one pass two of max_c M_c steps cuts every result at its own step
+      groups_one_graph = false;
+      enqueue_pass_one_group(op, B + c0 * n, kmax, nb, mem);
+      GroupHead g = fetch_group(op);
+      GroupY Y(op, nb, m);
+      std::vector<int32_t> cut((size_t)kBatchNbMax * TPL_MULTI_MAX, 0);
+      int32_t Mc[kBatchNbMax] = {0, 0, 0, 0};
+      size_t Mmax = 0;
+      for (int c = 0; c < nb; ++c) {
+        const HostDecomp d = g.decomp((size_t)c);
+        if (d.flags[1]) fail_input("Input vector `b` must not be a zero vector.");
+        for (size_t i = 0; i < m; ++i) {
+          const size_t e = (c0 + (size_t)c) * m + i;
+          if (d.steps == 0) {
+            report(e, 0, false, 0);
+            continue;
+          }
+          const ShiftedCol sc = shifted_col(d, sigmas[i], tol);
+          std::copy(sc.y.begin(), sc.y.end(), Y.col(i, (size_t)c));
+          cut[(size_t)c * TPL_MULTI_MAX + i] = (int32_t)sc.steps;
+          Mc[c] = std::max(Mc[c], (int32_t)sc.steps);
+          if (res_out) std::copy(sc.res.begin(), sc.res.end(), res_out + e * kmax);
+          report(e, sc.steps, sc.converged, sc.res.size());
+        }
+        Mmax = std::max(Mmax, (size_t)Mc[c]);
+      }
+      for (int c = 0; c < nb; ++c) upload_col_count(op, c, &Mc[c]);
+      Y.upload(op);
+      HIPCHK(hipMemcpyAsync(op->d_bcut, cut.data(), cut.size() * sizeof(int32_t),
+                            hipMemcpyHostToDevice, op->stream));
+      run_pass2_batch_multi_cut(op, std::max<size_t>(Mmax, 1), nb, m);
+      download_group_multi(op, x_out + c0 * m * n, nb, m, mem);
+      sync_checked(op);
+      c0 += (size_t)nb;
+    }
+    // bit 5: every group of four or two ran as one graph; a lone column reports its own
+    if (any_group) op->last_one_graph = groups_one_graph;
+  });
+}
+
+tpl_status tpl_lanczos_pass_two_batch_multi_cut(tpl_op_t op, const double* B, int64_t b_len,
+                                                size_t s, const double* alphas,
+                                                const double* betas, size_t ld,
+                                                const size_t* steps, const double* b_norms,
+                                                const double* y, const size_t* col_steps,
+                                                size_t m, double* x_out, int mem) {
+  return guarded([&] {
+    if (!op || !B || !x_out || !steps || !b_norms || !col_steps || !y || !alphas)
+      fail(TPL_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (s == 0 || s > (size_t)TPL_BATCH_MAX)
+      fail(TPL_ERR_INVALID_ARGUMENT, "s must be between 1 and TPL_BATCH_MAX");
+    if (m == 0 || m > (size_t)TPL_MULTI_MAX)
+      fail(TPL_ERR_INVALID_ARGUMENT, "m must be between 1 and TPL_MULTI_MAX");
+    // the single call's checks of the counts and the decomposition, per column in ascending
+    // order, before anything touches a device
+    for (size_t c = 0; c < s; ++c) {
+      if (steps[c] == 0 || steps[c] > ld || steps[c] > (size_t)INT32_MAX / 2)
+        fail(TPL_ERR_INVALID_ARGUMENT, "steps[c] must be >= 1 and ld >= steps[c]");
+      for (size_t i = 0; i < m; ++i)
+        if (col_steps[c * m + i] < 1 || col_steps[c * m + i] > steps[c])
+          fail(TPL_ERR_INVALID_ARGUMENT,
+               "every col_steps[c m + i] must be between 1 and steps[c]");
+      if (b_norms[c] <= kBreakdownTol)
+        fail_input("The initial vector `b` must not be a zero vector.");
+      if (steps[c] > 1 && !betas)
+        fail(TPL_ERR_INVALID_ARGUMENT, "decomposition arrays shorter than steps_taken");
+    }
+    set_device(op);
+    if (op->dist) fail(TPL_ERR_UNSUPPORTED, "batch-multi solve of a partitioned operator");
+    check_b(op, B, b_len);
+    const TimingOff untimed(op);
+    const size_t n = (size_t)op->part.n;
+    for (size_t c0 = 0; c0 < s;) {
+      const int nb = n == 0 ? 1 : group_width(s - c0);
+      if (nb == 1) {  // the single pass two with a cut per column
+        const size_t st = steps[c0];
+        int32_t cs[TPL_MULTI_MAX];
+        for (size_t i = 0; i < m; ++i) cs[i] = (int32_t)col_steps[c0 * m + i];
+        pass_two_multi_cut_run(op, B + c0 * n, alphas + c0 * ld, betas ? betas + c0 * ld : nullptr,
+                               st, b_norms[c0], y + c0 * m * ld, ld, cs, m, x_out + c0 * m * n,
+                               mem);
+        ++c0;
+        continue;
+      }
+      size_t kmax = 1;
+      for (int c = 0; c < nb; ++c) kmax = std::max(kmax, steps[c0 + c]);
+      ensure_batch(op, nb, kmax);
+      ensure_batch_multi(op, m, mem != TPL_MEM_DEVICE);
+      ensure_batch_cut(op);
+      // decompositions -> the group's state (steps_c, ||b_c||, alphas, betas), y -> the
+      // table, the cuts -> the cut table
+      GroupHead g(op);
+      GroupY Y(op, nb, m);
+      std::vector<int32_t> cut((size_t)kBatchNbMax * TPL_MULTI_MAX, 0);
+      for (int c = 0; c < nb; ++c) {
+        const size_t cc = c0 + (size_t)c, st = steps[cc];
+        g.flags((size_t)c)[2] = (int32_t)st;
+        g.norms((size_t)c)[0] = b_norms[cc];
+        std::memcpy(g.alphas((size_t)c), alphas + cc * ld, st * sizeof(double));
+        if (st > 1) std::memcpy(g.betas((size_t)c), betas + cc * ld, (st - 1) * sizeof(double));
+        for (size_t i = 0; i < m; ++i) {
+          std::memcpy(Y.col(i, (size_t)c), y + (cc * m + i) * ld, st * sizeof(double));
+          cut[(size_t)c * TPL_MULTI_MAX + i] = (int32_t)col_steps[cc * m + i];
+        }
+      }
+      HIPCHK(hipMemcpyAsync(op->bat.d_state, g.h.data(), g.h.size() * sizeof(double),
+                            hipMemcpyHostToDevice, op->stream));
+      Y.upload(op);
+      HIPCHK(hipMemcpyAsync(op->d_bcut, cut.data(), cut.size() * sizeof(int32_t),
+                            hipMemcpyHostToDevice, op->stream));
+      upload_group(op, B + c0 * n, nb, mem);
+      run_pass2_batch_multi_cut(op, kmax, nb, m);
+      download_group_multi(op, x_out + c0 * m * n, nb, m, mem);
+      sync_checked(op);
+      c0 += (size_t)nb;
+    }
   });
 }
 

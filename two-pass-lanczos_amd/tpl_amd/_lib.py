@@ -298,3 +298,14 @@ tpl_op_ftk_inv_shifts_device = _sig("tpl_op_ftk_inv_shifts_device", c_int, c_voi
                                     c_size_t, PD, PD, c_size_t, PD)
 EXPORTED += ["tpl_lanczos_two_pass_shifted_inv_tol", "tpl_lanczos_pass_two_multi_cut",
              "tpl_op_ftk_inv_shifts_device"]
+tpl_lanczos_two_pass_batch_shifted_inv_tol = _sig(
+    "tpl_lanczos_two_pass_batch_shifted_inv_tol", c_int, c_void_p, c_void_p, c_int64, c_size_t,
+    c_size_t, PD, c_size_t, c_double, c_void_p, c_int, POINTER(c_size_t), POINTER(c_int32), PD,
+    POINTER(c_size_t))
+tpl_lanczos_pass_two_batch_multi_cut = _sig(
+    "tpl_lanczos_pass_two_batch_multi_cut", c_int, c_void_p, c_void_p, c_int64, c_size_t, PD, PD,
+    c_size_t, POINTER(c_size_t), PD, PD, POINTER(c_size_t), c_size_t, c_void_p, c_int)
+# the largest kmax at which auto mode runs a group of the batch shifted solve as one graph
+tpl_batch_shifted_inv_tol_auto_k = _sig("tpl_batch_shifted_inv_tol_auto_k", c_size_t)
+EXPORTED += ["tpl_lanczos_two_pass_batch_shifted_inv_tol", "tpl_lanczos_pass_two_batch_multi_cut",
+             "tpl_batch_shifted_inv_tol_auto_k"]

@@ -16,6 +16,7 @@ this module                            reference
 ``lanczos_pass_one_batch``             (none: pass one for s vectors b in lock-step)
 ``lanczos_pass_two_batch``             (none: pass two for s vectors b in lock-step)
 ``lanczos_pass_two_batch_multi``       (none: the same for m coefficient vectors per b)
+``lanczos_pass_two_batch_multi_cut``   (none: the same, result (c, i) cut to its own steps)
 =====================================  ================================================
 
 Every call runs the recurrence on the GPU through libtpl_amd.so (C ABI,
@@ -346,5 +347,59 @@ def lanczos_pass_two_batch_multi(operator, B, decompositions, Ys):
         op.handle, bv.ptr, bv.n, bv.s, alphas.ctypes.data_as(POINTER(c_double)),
         betas.ctypes.data_as(POINTER(c_double)), ld, steps,
         bnorms.ctypes.data_as(POINTER(c_double)), yy.ctypes.data_as(POINTER(c_double)), m,
+        Vec.ptr_of(x), bv.mem))
+    return x.permute(2, 1, 0) if hasattr(x, "permute") else x.transpose(2, 1, 0)
+
+
+def lanczos_pass_two_batch_multi_cut(operator, B, decompositions, Ys, col_steps):
+    """``lanczos_pass_two_batch_multi`` with a cut per (column, coefficient vector):
+    ``col_steps[c][i]`` (1 <= it <= ``decompositions[c].steps_taken``) is the number of steps
+    result (c, i) takes. ``X[:, i, c]`` is bitwise ``lanczos_pass_two`` of ``B[:, c]`` on
+    ``decompositions[c]`` cut to that many steps with ``Ys[c][:col_steps[c][i], i]``; the
+    entries of ``Ys[c][:, i]`` past the cut are never used. Returns shape (n, m, s)."""
+    bv = Cols(B)
+    bv.check_rows(operator)
+    decs, Ys = list(decompositions), list(Ys)
+    if len(decs) != bv.s or len(Ys) != bv.s:
+        raise ValueError("one decomposition and one Y per column of B")
+    yl = [y.detach().double().cpu().numpy() if hasattr(y, "is_cuda")
+          else np.asarray(y, dtype=np.float64) for y in Ys]
+    if any(y.ndim != 2 for y in yl):
+        raise ValueError("every Y must be a (steps, m) matrix")
+    m = yl[0].shape[1]
+    if m == 0 or any(y.shape[1] != m for y in yl):
+        raise ValueError("every Y must hold the same number (at least one) of columns")
+    cs = np.asarray(col_steps, dtype=np.int64)
+    if cs.shape != (bv.s, m):
+        raise ValueError("col_steps must hold one count per (column, coefficient vector)")
+    if np.any(cs < 0):
+        raise ValueError("col_steps must not be negative")
+    for d, y in zip(decs, yl):  # the single call's check, per column in ascending order
+        if int(d.steps_taken) != y.shape[0]:
+            raise LanczosError.parameter_mismatch("y_k", int(d.steps_taken), y.shape[0])
+    op = _op(operator)
+    ld = max([int(d.steps_taken) for d in decs] + [1])
+    alphas = np.zeros((bv.s, ld))
+    betas = np.zeros((bv.s, ld))
+    yy = np.zeros((bv.s, m, ld))  # column (c m + i) of the ld x (s m) table
+    steps = (c_size_t * bv.s)()
+    counts = (c_size_t * (bv.s * m))(*[int(v) for v in cs.reshape(-1)])
+    bnorms = np.zeros(bv.s)
+    for c, (d, y) in enumerate(zip(decs, yl)):
+        st = int(d.steps_taken)
+        a = np.asarray(d.alphas, dtype=np.float64).reshape(-1)
+        b = np.asarray(d.betas, dtype=np.float64).reshape(-1)
+        if a.shape[0] < st or b.shape[0] + 1 < st:
+            raise ValueError("decomposition arrays shorter than steps_taken")
+        alphas[c, :st] = a[:st]
+        betas[c, :max(st - 1, 0)] = b[:max(st - 1, 0)]
+        yy[c, :, :st] = y.T
+        steps[c] = st
+        bnorms[c] = float(d.b_norm)
+    x = bv.empty(bv.s, m, bv.n)
+    check(_lib.tpl_lanczos_pass_two_batch_multi_cut(
+        op.handle, bv.ptr, bv.n, bv.s, alphas.ctypes.data_as(POINTER(c_double)),
+        betas.ctypes.data_as(POINTER(c_double)), ld, steps,
+        bnorms.ctypes.data_as(POINTER(c_double)), yy.ctypes.data_as(POINTER(c_double)), counts, m,
         Vec.ptr_of(x), bv.mem))
     return x.permute(2, 1, 0) if hasattr(x, "permute") else x.transpose(2, 1, 0)

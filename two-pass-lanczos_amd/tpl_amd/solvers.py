@@ -42,6 +42,11 @@ stopped at its own step m*_i. It returns shape (n, m) with strides (1, n).
 ``lanczos_two_pass_batch_exp_times(operator, B, k, ts)`` (no reference counterpart) is the same
 for the s columns of ``B`` in lock-step: exp(t_i A) b_c, every exp(t_i T_k) e_1 of a group of
 columns evaluated by one device launch. It returns shape (n, m, s) with strides (1, n, n m).
+
+``lanczos_two_pass_batch_shifted_inv_tol(operator, B, kmax, sigmas, tol)`` (no reference
+counterpart) is ``lanczos_two_pass_shifted_inv_tol`` for the s columns of ``B`` in lock-step:
+(A + sigma_i I)^{-1} b_c, every (column, shift) stopped at its own step. It returns shape
+(n, m, s) with strides (1, n, n m).
 """
 from __future__ import annotations
 
@@ -252,3 +257,43 @@ def lanczos_two_pass_batch_exp_times(operator, B, k: int, ts, return_on_device: 
         bv.mem, on.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
     X = x.permute(2, 1, 0) if hasattr(x, "permute") else x.transpose(2, 1, 0)
     return (X, on.reshape(bv.s, m).T.astype(bool)) if return_on_device else X
+
+
+def lanczos_two_pass_batch_shifted_inv_tol(operator, B, kmax: int, sigmas, tol: float,
+                                           return_info: bool = False):
+    """(A + sigma_i I)^{-1} b_c for the m shifts ``sigmas`` and every column c of ``B`` (n x s)
+    by ONE run: per group of columns pass one on A in lock-step, every (column, shift) stopped at
+    the first step m*_{c,i} whose relative Lanczos residual is <= ``tol`` (or at the steps
+    column c took), one pass two that cuts each of the group's results at its own step.
+    ``X[:, i, c]`` is bitwise ``lanczos_two_pass_shifted_inv_tol(operator, B[:, c], kmax,
+    sigmas, tol)[:, i]``, whatever s, m and the other columns hold. On one GPU within the
+    device-inv bounds (``set_device_ftk``) a group is one graph: the elimination workgroup of
+    pass one runs one lane per (column, shift), a column stops storing when all its shifts have
+    met the tolerance, and the launches left when every column has stopped return at once.
+    Returns shape (n, m, s) as ``lanczos_two_pass_batch_multi``; with ``return_info`` also a
+    dict: ``steps`` ((m, s) int array of m*_{c,i}), ``converged`` ((m, s) bool array) and
+    ``residuals`` (``residuals[c][i]``: the history of (c, i) up to the last entry formed)."""
+    sg = np.ascontiguousarray(np.atleast_1d(np.asarray(sigmas, dtype=np.float64)).reshape(-1))
+    m = int(sg.shape[0])
+    if m == 0:
+        raise ValueError("sigmas must hold at least one shift")
+    bv = Cols(B)
+    bv.check_rows(operator)
+    operator = as_operator(operator)
+    s = bv.s
+    x = bv.empty(s, m, bv.n)  # C-order (s, m, n) == column-major n x (s m), column c m + i
+    kcap = max(int(kmax), 1)
+    res = np.zeros((max(s * m, 1), kcap), dtype=np.float64)  # column-major (kmax, s m)
+    steps = (ctypes.c_size_t * max(s * m, 1))()
+    rlen = (ctypes.c_size_t * max(s * m, 1))()
+    conv = (ctypes.c_int32 * max(s * m, 1))()
+    check(_lib.tpl_lanczos_two_pass_batch_shifted_inv_tol(
+        operator.handle, bv.ptr, bv.n, s, kmax, sg.ctypes.data_as(_lib.PD), m, float(tol),
+        Vec.ptr_of(x), bv.mem, steps, conv, res.ctypes.data_as(_lib.PD), rlen))
+    X = x.permute(2, 1, 0) if hasattr(x, "permute") else x.transpose(2, 1, 0)
+    if not return_info:
+        return X
+    return X, {"steps": np.array(steps[:s * m], dtype=np.int64).reshape(s, m).T,
+               "converged": np.array(conv[:s * m], dtype=bool).reshape(s, m).T,
+               "residuals": [[res[c * m + i, : rlen[c * m + i]].copy() for i in range(m)]
+                             for c in range(s)]}
