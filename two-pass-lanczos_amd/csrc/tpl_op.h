@@ -302,6 +302,13 @@ void dev_free(tpl_op_s* op, T*& p) {
   hipFree(p);
   p = nullptr;
 }
+// Zeroes of a new allocation, in the order of the operator's stream. That stream is
+// non-blocking: a hipMemset on the null stream is ordered neither with it nor, for device
+// memory, with the host, so it can land after the first upload the call enqueues into the
+// same buffer (seen: the cuts of a first tpl_lanczos_pass_two_multi_cut read back as zeros).
+inline void dev_zero(tpl_op_s* op, void* p, size_t bytes) {
+  if (bytes) HIPCHK(hipMemsetAsync(p, 0, bytes, op->stream));
+}
 uint64_t device_bytes(const tpl_op_s* op);
 
 void rebuild_schedule(tpl_op_s* op, const SchedParams& cand, int reorder);

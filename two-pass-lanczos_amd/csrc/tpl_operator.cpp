@@ -285,7 +285,7 @@ void alloc_cache(tpl_op_s* op, SolverState& s, size_t rows) {
   const size_t sums = rows * lr.size() * sizeof(double);
   const size_t table = op->lay.s_identity ? 0 : (lr.size() * sizeof(int32_t) + 7) / 8 * 8;
   dev_alloc(op, &s.d_ycache, sums + table);
-  HIPCHK(hipMemset(s.d_ycache, 0, sums));
+  dev_zero(op, s.d_ycache, sums);
   if (table) {
     s.d_ylrow = reinterpret_cast<int32_t*>(s.d_ycache + rows * lr.size());
     HIPCHK(hipMemcpy(s.d_ylrow, lr.data(), lr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -329,7 +329,7 @@ void ensure_state(tpl_op_s* op, size_t k, bool reorth) {
     SolverState ns;  // the new state; after the swap below, the old one
     try {
       dev_alloc(op, &ns.d_state, bytes);
-      HIPCHK(hipMemset(ns.d_state, 0, bytes));
+      dev_zero(op, ns.d_state, bytes);
       HIPCHK(hipHostMalloc(&ns.h_state, kFlagBytes + (4 * kc + 1) * sizeof(double),
                            hipHostMallocDefault));
       alloc_cache(op, ns, wanted_cache_rows(op, kc));
@@ -402,7 +402,7 @@ namespace {
 void ensure_exp_ts(tpl_op_s* op) {
   if (op->d_exp_ts) return;
   dev_alloc(op, &op->d_exp_ts, TPL_MULTI_MAX * sizeof(double));
-  HIPCHK(hipMemset(op->d_exp_ts, 0, TPL_MULTI_MAX * sizeof(double)));
+  dev_zero(op, op->d_exp_ts, TPL_MULTI_MAX * sizeof(double));
 }
 } // namespace
 void ensure_exp_times_batch(tpl_op_s* op) {
@@ -410,7 +410,7 @@ void ensure_exp_times_batch(tpl_op_s* op) {
   ensure_exp_ts(op);
   if (!op->d_expb_back) {
     dev_alloc(op, &op->d_expb_back, bytes);
-    HIPCHK(hipMemset(op->d_expb_back, 0, bytes));
+    dev_zero(op, op->d_expb_back, bytes);
   }
   if (!op->h_expb_back)
     HIPCHK(hipHostMalloc((void**)&op->h_expb_back, bytes, hipHostMallocDefault));
@@ -419,7 +419,7 @@ void ensure_exp_times(tpl_op_s* op) {
   ensure_exp_ts(op);
   if (!op->d_exp_back) {
     dev_alloc(op, &op->d_exp_back, TPL_MULTI_MAX * sizeof(int32_t));
-    HIPCHK(hipMemset(op->d_exp_back, 0, TPL_MULTI_MAX * sizeof(int32_t)));
+    dev_zero(op, op->d_exp_back, TPL_MULTI_MAX * sizeof(int32_t));
   }
   if (!op->h_exp_back)
     HIPCHK(hipHostMalloc((void**)&op->h_exp_back, TPL_MULTI_MAX * sizeof(int32_t),
@@ -434,14 +434,14 @@ void ensure_tol(tpl_op_s* op) {
   op->h_tol = nullptr;
   op->tol_cap = 0;
   dev_alloc(op, &op->d_tol, (1 + kc) * sizeof(double));
-  HIPCHK(hipMemset(op->d_tol, 0, (1 + kc) * sizeof(double)));
+  dev_zero(op, op->d_tol, (1 + kc) * sizeof(double));
   HIPCHK(hipHostMalloc(&op->h_tol, kFlagBytes + kc * sizeof(double), hipHostMallocDefault));
   op->tol_cap = kc;
 }
 void ensure_col_steps(tpl_op_s* op) {
   if (op->d_col_steps) return;
   dev_alloc(op, &op->d_col_steps, TPL_MULTI_MAX * sizeof(int32_t));
-  HIPCHK(hipMemset(op->d_col_steps, 0, TPL_MULTI_MAX * sizeof(int32_t)));
+  dev_zero(op, op->d_col_steps, TPL_MULTI_MAX * sizeof(int32_t));
 }
 launch::ShiftTol ensure_stol(tpl_op_s* op, size_t m) {
   const size_t kc = op->st.kcap;
@@ -455,7 +455,7 @@ launch::ShiftTol ensure_stol(tpl_op_s* op, size_t m) {
     const size_t doubles = 1 + mc * (4 + 5 * kc);
     const size_t bytes = doubles * sizeof(double) + 2 * mc * sizeof(int32_t);
     dev_alloc(op, &op->d_stol, bytes);
-    HIPCHK(hipMemset(op->d_stol, 0, bytes));
+    dev_zero(op, op->d_stol, bytes);
     HIPCHK(hipHostMalloc(&op->h_stol,
                          kFlagBytes + 2 * mc * sizeof(int32_t) + kc * mc * sizeof(double),
                          hipHostMallocDefault));
@@ -507,7 +507,7 @@ void alloc_batch_cache(tpl_op_s* op, double** ycache, int32_t** ylrow, int w, si
   const size_t sums = rows * lr.size() * (size_t)w * sizeof(double);
   const size_t table = op->lay.s_identity ? 0 : (lr.size() * sizeof(int32_t) + 7) / 8 * 8;
   dev_alloc(op, ycache, sums + table);
-  HIPCHK(hipMemset(*ycache, 0, sums));
+  dev_zero(op, *ycache, sums);
   if (table) {
     *ylrow = reinterpret_cast<int32_t*>(*ycache + rows * lr.size() * (size_t)w);
     HIPCHK(hipMemcpy(*ylrow, lr.data(), lr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -527,9 +527,9 @@ void ensure_batch_multi(tpl_op_s* op, size_t m, bool stage) {
     b.mcols = 0;
     try {
       dev_alloc(op, &b.d_mx, cols * (size_t)op->ld * w * sizeof(double));
-      HIPCHK(hipMemset(b.d_mx, 0, cols * (size_t)op->ld * w * sizeof(double)));
+      dev_zero(op, b.d_mx, cols * (size_t)op->ld * w * sizeof(double));
       dev_alloc(op, &b.d_my, cols * w * b.kcap * sizeof(double));
-      HIPCHK(hipMemset(b.d_my, 0, cols * w * b.kcap * sizeof(double)));
+      dev_zero(op, b.d_my, cols * w * b.kcap * sizeof(double));
     } catch (...) {
       dev_free(op, b.d_mx), dev_free(op, b.d_my);
       throw;
@@ -549,7 +549,7 @@ void ensure_batch_cut(tpl_op_s* op) {
   if (op->d_bcut) return;
   constexpr size_t bytes = (size_t)kBatchNbMax * TPL_MULTI_MAX * sizeof(int32_t);
   dev_alloc(op, &op->d_bcut, bytes);
-  HIPCHK(hipMemset(op->d_bcut, 0, bytes));
+  dev_zero(op, op->d_bcut, bytes);
 }
 launch::BatchShiftTol ensure_batch_stol(tpl_op_s* op, size_t m) {
   BatchBufs& b = op->bat;
@@ -566,7 +566,7 @@ launch::BatchShiftTol ensure_batch_stol(tpl_op_s* op, size_t m) {
     const size_t doubles = 1 + mc + w * mc * (3 + 5 * kc);
     const size_t bytes = doubles * sizeof(double) + w * 2 * mc * sizeof(int32_t);
     dev_alloc(op, &b.d_stol, bytes);
-    HIPCHK(hipMemset(b.d_stol, 0, bytes));
+    dev_zero(op, b.d_stol, bytes);
     HIPCHK(hipHostMalloc(&b.h_stol,
                          w * (kFlagBytes + 2 * mc * sizeof(int32_t) + kc * mc * sizeof(double)),
                          hipHostMallocDefault));
@@ -623,17 +623,17 @@ void ensure_batch(tpl_op_s* op, int nb, size_t k) {
   const size_t ld = (size_t)op->ld, na = (size_t)std::max(A.NA, 1), g2 = (size_t)std::max(A.G2, 1);
   try {
     dev_alloc(op, &b.d_vecs, 6 * ld * w * sizeof(double));
-    HIPCHK(hipMemset(b.d_vecs, 0, 6 * ld * w * sizeof(double)));
+    dev_zero(op, b.d_vecs, 6 * ld * w * sizeof(double));
     const size_t head = (size_t)w * (kFlagBytes / sizeof(double)) + (size_t)w * (4 * kc + 1);
     const size_t p2c_off = (head + 7) / 8 * 8;
     const size_t doubles = p2c_off + 8 * (size_t)w * kc + (size_t)w * (na + g2);
     dev_alloc(op, &b.d_state, doubles * sizeof(double));
-    HIPCHK(hipMemset(b.d_state, 0, doubles * sizeof(double)));
+    dev_zero(op, b.d_state, doubles * sizeof(double));
     const size_t nl = std::max<size_t>(op->lay.lrows.size(), 1);
     dev_alloc(op, &b.d_P, nl * kSlotStride * kBatchNbMax * sizeof(double));
-    HIPCHK(hipMemset(b.d_P, 0, nl * kSlotStride * kBatchNbMax * sizeof(double)));
+    dev_zero(op, b.d_P, nl * kSlotStride * kBatchNbMax * sizeof(double));
     dev_alloc(op, &b.d_Pcnt, nl * kCntStride * sizeof(unsigned int));
-    HIPCHK(hipMemset(b.d_Pcnt, 0, nl * kCntStride * sizeof(unsigned int)));
+    dev_zero(op, b.d_Pcnt, nl * kCntStride * sizeof(unsigned int));
     dev_alloc(op, &b.d_stage, std::max<size_t>((size_t)op->part.n, 1) * w * sizeof(double));
     double* p = b.d_vecs;
     b.b = p, p += ld * w;
@@ -771,7 +771,7 @@ void init_op(tpl_op_s* op) {
       op->part.halo ? (size_t)op->ld + (size_t)g.R * op->part.hH : (size_t)g.R * op->ld;
   const size_t gathered = 8 * gl, local = 2 * (size_t)op->ld;
   dev_alloc(op, &op->d_vecs, (gathered + local) * sizeof(double));
-  HIPCHK(hipMemset(op->d_vecs, 0, (gathered + local) * sizeof(double)));
+  dev_zero(op, op->d_vecs, (gathered + local) * sizeof(double));
   double* p = op->d_vecs;
   const size_t own = (size_t)(g.blocks ? op->dist->rank : 0) * op->ld;
   upload(op, &op->d_halo_send, op->part.halo_send);
@@ -793,7 +793,7 @@ void init_op(tpl_op_s* op) {
     const size_t nr = (size_t)op->dist->nranks;
     const size_t cnt = 2 * nr + (op->part.hybrid ? (size_t)long_epi_blocks(op) : 0);
     dev_alloc(op, &op->d_rsum, cnt * sizeof(double));
-    HIPCHK(hipMemset(op->d_rsum, 0, cnt * sizeof(double)));
+    dev_zero(op, op->d_rsum, cnt * sizeof(double));
     if (op->part.hybrid) {
       // every rank's chunk count (each rank's short rows are a contiguous block of the
       // global split, chunked by kChunkRows: every rank computes all counts alike)
@@ -806,7 +806,7 @@ void init_op(tpl_op_s* op) {
       // pass one strides the all-gather by y_ld1, pass two and tpl_op_apply by n_long + 1
       const size_t ya = nr * (size_t)std::max<int64_t>(op->y_ld1, (int64_t)op->lay.lrows.size() + 1);
       dev_alloc(op, &op->d_yall, ya * sizeof(double));
-      HIPCHK(hipMemset(op->d_yall, 0, ya * sizeof(double)));
+      dev_zero(op, op->d_yall, ya * sizeof(double));
       // the β stage all-gathers every rank's norm partials (each rank computes all ranks'
       // counts from the global split) and k_p1_spmv reduces each rank's with the tree the
       // rank-total launch applied — one launch less per pass-one step, the same bits —
@@ -818,13 +818,14 @@ void init_op(tpl_op_s* op) {
       if (op->dist->nranks <= kPbRanks && g2max <= kTPB) {
         op->pb_ld = g2max;
         dev_alloc(op, &op->d_pball, nr * (size_t)g2max * sizeof(double));
-        HIPCHK(hipMemset(op->d_pball, 0, nr * (size_t)g2max * sizeof(double)));
+        dev_zero(op, op->d_pball, nr * (size_t)g2max * sizeof(double));
       }
     }
   }
   HIPCHK(hipEventCreate(&op->ev0));
   HIPCHK(hipEventCreate(&op->ev1));
   for (hipEvent_t& e : op->tev) HIPCHK(hipEventCreate(&e));
+  sync_checked(op);  // the zeroes above are in place when the create returns
 }
 
 // The one way to make an operator: `part` on ctx's device and stream, as a rank of `dist`

@@ -214,6 +214,9 @@ static void enqueue_pass2_fused(tpl_op_s* op, size_t steps) {
                                op->stream));
 }
 void enqueue_pass2(tpl_op_s* op, size_t steps, double* Vout) {
+  // the step launches, never fused: tpl_op_flags bits 8 and 9 tell of this pass two
+  op->last_long_cache = steps >= 2 && long_cache_steps(op) > 0;
+  op->last_fused_p2 = false;
   enqueue_pass2_init(op, steps, Vout);
   enqueue_pass2_steps(op, steps, Vout);
 }
@@ -343,6 +346,7 @@ void run_pass2_multi(tpl_op_s* op, size_t steps, size_t m) {
   if (m == 0 || m > op->xcols || steps > op->ycap || m > TPL_MULTI_MAX)
     fail(TPL_ERR_INVALID_ARGUMENT, "run_pass2_multi: buffers smaller than the request");
   op->last_long_cache = steps >= 2 && long_cache_steps(op) > 0;
+  op->last_fused_p2 = false;
   run_graph(op, kGPass2Multi + graph_cache_kind(op), steps * (TPL_MULTI_MAX + 1) + m,
             [&] { enqueue_pass2_multi(op, steps, m); });
 }
@@ -379,6 +383,7 @@ static void check_multi_cut(const tpl_op_s* op, size_t steps, size_t m) {
 void run_pass2_multi_cut(tpl_op_s* op, size_t steps, size_t m) {
   check_multi_cut(op, steps, m);
   op->last_long_cache = steps >= 2 && long_cache_steps(op) > 0;
+  op->last_fused_p2 = false;
   run_graph(op, kGPass2MultiCut + graph_cache_kind(op), steps * (TPL_MULTI_MAX + 1) + m,
             [&] { enqueue_pass2_multi_cut(op, steps, m, false); });
 }
@@ -393,6 +398,7 @@ void run_two_pass_shifted_inv_tol(tpl_op_s* op, size_t kmax, const launch::Shift
   check_multi_cut(op, kmax, m);
   const int ck = graph_cache_kind(op);
   op->last_long_cache = kmax >= 2 && ck != 0;
+  op->last_fused_p2 = false;
   run_graph(op, kGTwoPassShiftedInvTol + ck, kmax * (TPL_MULTI_MAX + 1) + m, [&] {
     enqueue_p1_prologue(op);
     for (int j = 1; j <= (int)kmax; ++j) {
@@ -460,6 +466,7 @@ void run_pass1_batch(tpl_op_s* op, size_t k, int nb) {
 void run_pass2_batch(tpl_op_s* op, size_t kmax, int nb) {
   check_batch(op, kmax, nb);
   op->last_long_cache = kmax >= 2 && batch_cache_steps(op) > 0;
+  op->last_fused_p2 = false;
   run_graph(op, kGPass2Batch + batch_graph_cache_kind(op), kmax * 8 + (size_t)nb,
             [&] { enqueue_pass2_batch(op, kmax, nb); });
 }
@@ -503,6 +510,7 @@ void run_pass2_batch_multi(tpl_op_s* op, const size_t* steps, int nb, size_t m) 
   if (m == 0 || m > op->bat.mcols || m > TPL_MULTI_MAX)
     fail(TPL_ERR_INVALID_ARGUMENT, "batch-multi group: buffers smaller than the request");
   op->last_long_cache = kmax >= 2 && batch_cache_steps(op) > 0;
+  op->last_fused_p2 = false;
   if (!even) {  // the launch list depends on every steps_c: not captured
     enqueue_pass2_batch_multi(op, steps, nb, m);
     return;
@@ -547,6 +555,7 @@ static void check_batch_multi_cut(const tpl_op_s* op, size_t steps, int nb, size
 void run_pass2_batch_multi_cut(tpl_op_s* op, size_t steps, int nb, size_t m) {
   check_batch_multi_cut(op, steps, nb, m);
   op->last_long_cache = steps >= 2 && batch_cache_steps(op) > 0;
+  op->last_fused_p2 = false;
   run_graph(op, kGPass2BatchMultiCut + batch_graph_cache_kind(op),
             (steps * 8 + (size_t)nb) * (TPL_MULTI_MAX + 1) + m,
             [&] { enqueue_pass2_batch_multi_cut(op, steps, nb, m); });
@@ -566,6 +575,7 @@ void run_two_pass_batch_shifted_inv_tol(tpl_op_s* op, size_t kmax, int nb,
   check_batch_multi_cut(op, kmax, nb, m);
   const int ck = batch_graph_cache_kind(op);
   op->last_long_cache = kmax >= 2 && ck != 0;
+  op->last_fused_p2 = false;
   run_graph(op, kGTwoPassBatchShiftedInvTol + ck,
             (kmax * 8 + (size_t)nb) * (TPL_MULTI_MAX + 1) + m, [&] {
     const CsrDev A = csr_dev(op);
@@ -639,7 +649,7 @@ void run_two_pass_dev(tpl_op_s* op, size_t k, int f) {
   const bool stamped = !op->dist && stamp_first(k) > 0;
   if (stamped && !op->d_stamps) {
     dev_alloc(op, &op->d_stamps, 32 * sizeof(unsigned long long));
-    HIPCHK(hipMemset(op->d_stamps, 0, 32 * sizeof(unsigned long long)));
+    dev_zero(op, op->d_stamps, 32 * sizeof(unsigned long long));
   }
   run_pass1_graph(op, k, elim | (stamped ? kP1Stamped : 0));
   op->p1_samples = stamped ? kStampSteps : 0;
