@@ -11,7 +11,7 @@
 //   k_p2_xacc_cut     k_p2_xacc with a per-column cut: term t of column c only where
 //                     t < m*_c
 // Every entry of a shifted tridiagonal is alphas[j] + sigma_s, one IEEE addition, here as on
-// the host (tpl_solvers.cpp); nothing else ever forms it.
+// the host (tpl_solvers.cpp shifted_col); nothing else ever forms it.
 //
 // k_p1_axpy_stol repeats k_p1_axpy_tol's text (tpl_k_p1_tol.hip), which repeats k_p1_axpy's
 // (tpl_kernels.hip), for the reason given there: the existing instances must keep their

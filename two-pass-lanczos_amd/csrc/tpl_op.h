@@ -1,7 +1,9 @@
 // tpl_op.h — the handles behind the C ABI (include/tpl.h) and the helpers the host units
 // share. Internal: tpl_operator.cpp (lifetime, buffers, schedule), tpl_dist.cpp (the
-// rank-to-rank transport), tpl_passes.cpp (launch sequences, graph cache), tpl_solvers.cpp
-// (solver entry points) and tpl_profile.cpp (timing, profiling, tuning) include it.
+// rank-to-rank transport), tpl_passes.cpp (launch sequences, graph cache), the solver entry
+// points — tpl_solvers.cpp (one column), tpl_solvers_multi.cpp (m functions of one b),
+// tpl_solvers_batch.cpp (s right-hand sides), tpl_ftk_device.cpp (device f(T_k) probes), through
+// tpl_solve.h (the steps they share) — and tpl_profile.cpp (timing, profiling, tuning) include it.
 //
 // Ownership: each handle's destructor releases what the handle owns, and nothing else
 // does — tpl_*_destroy set the device, synchronise and delete, and a create that throws
