@@ -102,6 +102,31 @@ int tpl_device_count(void);
 tpl_status tpl_op_create_csr(tpl_ctx_t ctx, int64_t n, int64_t nnz,
                              const int64_t* row_ptr, const int32_t* col_idx,
                              const double* vals, tpl_op_t* out);
+/* ---- dense operator: replaces faer `LinOp<f64>` for a dense `Mat<f64>` (the reference's
+ *      tests/correctness.rs and src/bin/dense_tradeoff.rs). Element (i, j) is a[i*lda + j];
+ *  A must be SYMMETRIC (not checked, as for CSR), which makes row- and column-major the same
+ *  thing: faer's column-major Mat passes straight through with lda = its column stride.
+ *  mem: TPL_MEM_HOST or TPL_MEM_DEVICE; `a` is borrowed for the call only. The device keeps
+ *  the matrix whole (8 bytes per entry, rows a padded leading dimension apart; counted in
+ *  tpl_op_device_bytes) and streams it once per step: no indices, no gathers.
+ *  Reduction order: every row is a long row of the canonical order (tpl_op_schedule:
+ *  n_short = 0, long_rows = 0 .. n-1, tpl_op_permutation the identity) over all n columns,
+ *  explicit zeros included, in S = tpl_op_slices column slices (tpl_dense_schedule's rule;
+ *  tpl_op_set_slices works). tpl_op_nnz is n * n; tpl_op_flags bit 10 is set.
+ *  Runs tpl_op_apply and every single-right-hand-side solver. Refused with
+ *  TPL_ERR_UNSUPPORTED before any device work: every *_batch* entry point,
+ *  tpl_op_set_schedule, tpl_op_set_reorder(1), tpl_op_tune_order, tpl_op_set_order_groups,
+ *  tpl_op_set_value_format, tpl_op_set_long_cache(1) and tpl_profile_kernel; the auto modes
+ *  of the locality order, the long-row cache and the fused pass two resolve to off.
+ *  Errors: NULL argument, n <= 0, lda < n: TPL_ERR_INVALID_ARGUMENT; n >= 2^31:
+ *  TPL_ERR_UNSUPPORTED; TPL_ERR_OUT_OF_MEMORY leaves nothing behind.                    */
+tpl_status tpl_op_create_dense(tpl_ctx_t ctx, int64_t n, const double* a, int64_t lda, int mem,
+                               tpl_op_t* out);
+/* The schedule rule of a dense operator of n rows (host only): *slices = slices_req (1, 2,
+ * 4, 8), or for 0 the CSR auto rule (1 up to 65 536 columns); (*G2, *E) the element-wise
+ * geometry of n rows under the default schedule parameters. Outputs may be NULL.          */
+tpl_status tpl_dense_schedule(int64_t n, int32_t slices_req, int32_t* slices, int32_t* G2,
+                              int64_t* E);
 tpl_status tpl_op_destroy(tpl_op_t op);
 int64_t tpl_op_nrows(tpl_op_t op); /* LinOp::nrows / ncols */
 int64_t tpl_op_nnz(tpl_op_t op);
@@ -118,7 +143,8 @@ int64_t tpl_op_nnz(tpl_op_t op);
  * from the long-row cache (tpl_op_set_long_cache: a two-pass solve whose bit is in
  * tpl_op_set_long_cache_solvers' mask — by default tpl_lanczos_two_pass alone — with the
  * cache on; any other entry point's pass two reads 0), bit 9: that pass two ran fused — two
- * launches for all its steps (tpl_op_set_fused_pass_two; bit 8 is set as well).
+ * launches for all its steps (tpl_op_set_fused_pass_two; bit 8 is set as well), bit 10: a
+ * dense operator (tpl_op_create_dense; bits 6, 8 and 9 read 0 on it).
  * -1 if op is NULL.                                                                    */
 int tpl_op_flags(tpl_op_t op);
 /* Locality order (single-GPU operators; rebuilds the layout). mode 1: the device

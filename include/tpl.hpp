@@ -332,10 +332,30 @@ class HipCsrOp {
   }
   tpl_op_t handle() const { return op_; }
 
- private:
-  HipCsrOp() = default;
+ protected:
+  HipCsrOp() = default;  // DenseOp: the same handle, created by tpl_op_create_dense
   tpl_op_t op_ = nullptr;
+
+ private:
   std::shared_ptr<Dist> dist_;  // partitioned operators: keeps the communicator alive
+};
+
+// A symmetric dense matrix resident in HBM (faer LinOp<f64> on Mat<f64>: the reference's
+// tests/correctness.rs and src/bin/dense_tradeoff.rs), built from the Mat mirror. The engine
+// handle is the one every solver takes, so every single-right-hand-side function of this
+// header accepts a DenseOp where it takes a HipCsrOp; the *_batch* ones throw the engine's
+// refusal (EngineError, TPL_ERR_UNSUPPORTED). A is symmetric, so the column-major Mat is read
+// in place as its row-major transpose (lda = rows).
+class DenseOp : public HipCsrOp {
+ public:
+  DenseOp(const Context& ctx, const Mat& a) {
+    if (a.rows != a.cols || a.data.size() != a.rows * a.cols)
+      throw EngineError(TPL_ERR_INVALID_ARGUMENT, "a dense operator must be square");
+    detail::check(tpl_op_create_dense(ctx.handle(), (int64_t)a.rows, a.data.data(),
+                                      (int64_t)a.rows, TPL_MEM_HOST, &op_));
+  }
+  // Column slices of a row's sum (tpl_op_set_slices): 1, 2, 4, 8, or 0 for the auto rule.
+  void set_slices(int32_t slices) { detail::check(tpl_op_set_slices(op_, slices)); }
 };
 
 namespace detail {

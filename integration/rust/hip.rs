@@ -105,6 +105,8 @@ extern "C" {
     fn tpl_ctx_destroy(ctx: *mut TplCtx) -> c_int;
     fn tpl_op_create_csr(ctx: *mut TplCtx, n: i64, nnz: i64, row_ptr: *const i64,
                          col_idx: *const i32, vals: *const f64, out: *mut *mut TplOp) -> c_int;
+    fn tpl_op_create_dense(ctx: *mut TplCtx, n: i64, a: *const f64, lda: i64, mem: c_int,
+                           out: *mut *mut TplOp) -> c_int;
     fn tpl_op_destroy(op: *mut TplOp) -> c_int;
     fn tpl_op_apply(op: *mut TplOp, x: *const f64, y: *mut f64, mem: c_int) -> c_int;
     fn tpl_lanczos(op: *mut TplOp, b: *const f64, b_len: i64, k: usize, f: FtkFn,
@@ -557,6 +559,139 @@ impl<'a> HipOperand for SparseColMatRef<'a, usize, f64> {
 }
 
 impl HipOperand for SparseColMat<usize, f64> {
+    fn with_hip_op<R, G: FnOnce(&HipCsrOp) -> R>(&self, g: G) -> Result<R, LanczosError> {
+        self.as_ref().with_hip_op(g)
+    }
+}
+
+/// Device-resident dense symmetric operator (tpl_op_create_dense): faer's `LinOp<f64>` for the
+/// dense `Mat<f64>` of tests/correctness.rs and src/bin/dense_tradeoff.rs. The engine handle
+/// is the one every solver of this module takes, so the operator is its handle and nothing
+/// else: every single-right-hand-side function below accepts `&HipDenseOp`; the `*_batch*`
+/// ones return the engine's refusal (TPL_ERR_UNSUPPORTED, as a SolverError).
+#[derive(Debug)]
+pub struct HipDenseOp {
+    handle: HipCsrOp,
+}
+
+impl HipDenseOp {
+    /// Upload the symmetric `a` once. A is symmetric, so a column-major `Mat` (faer's own
+    /// layout, row stride 1) is read in place as its row-major transpose with lda = the
+    /// column stride; any other striding is copied first.
+    pub fn from_mat(a: MatRef<'_, f64>, device: i32) -> Result<Self, LanczosError> {
+        if a.nrows() != a.ncols() {
+            return Err(LanczosError(LanczosErrorKind::DimensionMismatch {
+                operator_cols: a.ncols(),
+                vector_rows: a.nrows(),
+            }));
+        }
+        let n = a.nrows();
+        let (rs, cs) = (a.row_stride(), a.col_stride());
+        let copy: Vec<f64>;
+        let (ptr, lda) = if n > 0 && rs == 1 && cs >= n as isize {
+            (a.as_ptr(), cs as i64)
+        } else if n > 0 && cs == 1 && rs >= n as isize {
+            (a.as_ptr(), rs as i64)
+        } else {
+            copy = (0..n * n).map(|e| a[(e / n, e % n)]).collect();
+            (copy.as_ptr(), n as i64)
+        };
+        let mut ctx = std::ptr::null_mut();
+        let mut op = std::ptr::null_mut();
+        unsafe {
+            check(tpl_ctx_create(device, &mut ctx))?;
+            if let Err(e) = check(tpl_op_create_dense(ctx, n as i64, ptr, lda, TPL_MEM_HOST,
+                                                      &mut op)) {
+                tpl_ctx_destroy(ctx);
+                return Err(e);
+            }
+        }
+        Ok(Self { handle: HipCsrOp { ctx, op, n, lock: Arc::new(Mutex::new(())), dist: None } })
+    }
+
+    pub fn nrows(&self) -> usize {
+        self.handle.n
+    }
+
+    /// y = A x for one host vector (the per-call compatibility path).
+    pub fn apply_vec(&self, x: &[f64]) -> Result<Vec<f64>, LanczosError> {
+        self.handle.apply_vec(x)
+    }
+}
+
+/// faer's `LinOp<f64>` over `tpl_op_apply`, as for [`HipCsrOp`].
+impl LinOp<f64> for HipDenseOp {
+    fn apply_scratch(&self, rhs_ncols: usize, par: Par) -> StackReq {
+        self.handle.apply_scratch(rhs_ncols, par)
+    }
+    fn nrows(&self) -> usize {
+        self.handle.n
+    }
+    fn ncols(&self) -> usize {
+        self.handle.n
+    }
+    fn apply(&self, out: MatMut<'_, f64>, rhs: MatRef<'_, f64>, par: Par, stack: &mut MemStack) {
+        LinOp::apply(&self.handle, out, rhs, par, stack)
+    }
+    fn conj_apply(&self, out: MatMut<'_, f64>, rhs: MatRef<'_, f64>, par: Par,
+                  stack: &mut MemStack) {
+        LinOp::apply(&self.handle, out, rhs, par, stack) // real: conj(A) = A
+    }
+}
+
+impl HipOperand for HipDenseOp {
+    fn with_hip_op<R, G: FnOnce(&HipCsrOp) -> R>(&self, g: G) -> Result<R, LanczosError> {
+        Ok(g(&self.handle))
+    }
+}
+
+thread_local! {
+    /// The last dense faer matrix uploaded on this thread: (operand key, operator).
+    static UPLOADED_DENSE: RefCell<Option<([u64; 4], HipDenseOp)>> = const { RefCell::new(None) };
+}
+
+/// The identity of a dense `a` as this thread last uploaded it: its address, dimension and
+/// strides, and an FNV-1a checksum of KEY_SAMPLES evenly spaced entries — O(KEY_SAMPLES) host
+/// work per solver call, as for the sparse operand (`refresh_uploaded_dense` after changing
+/// values in place).
+fn dense_operand_key(a: MatRef<'_, f64>) -> [u64; 4] {
+    let n = a.nrows();
+    let mut h = 0xcbf29ce484222325u64;
+    let total = n * n;
+    let samples = KEY_SAMPLES.min(total);
+    for s in 0..samples {
+        let e = ((s as u128 * total as u128) / samples as u128) as usize;
+        h = (h ^ a[(e / n, e % n)].to_bits()).wrapping_mul(0x100000001b3);
+    }
+    [a.as_ptr() as usize as u64, n as u64,
+     (a.row_stride() as i64 as u64) ^ ((a.col_stride() as i64 as u64) << 32), h]
+}
+
+/// Forget this thread's upload of a dense faer matrix: the next solver call uploads it again.
+pub fn refresh_uploaded_dense() {
+    UPLOADED_DENSE.with(|cell| *cell.borrow_mut() = None);
+}
+
+/// The reference's dense call sites (src/bin/dense_tradeoff.rs, tests/correctness.rs) pass
+/// `&a.as_ref()` of a `Mat<f64>`: upload on first use (device 0, or `TPL_DEVICE`), reuse while
+/// the operand key is unchanged.
+impl<'a> HipOperand for MatRef<'a, f64> {
+    fn with_hip_op<R, G: FnOnce(&HipCsrOp) -> R>(&self, g: G) -> Result<R, LanczosError> {
+        let key = dense_operand_key(*self);
+        UPLOADED_DENSE.with(|cell| {
+            let mut slot = cell.borrow_mut();
+            if !matches!(&*slot, Some((k, _)) if *k == key) {
+                *slot = None; // free the previous upload before the new one
+                let device = std::env::var("TPL_DEVICE").ok()
+                    .and_then(|s| s.parse().ok()).unwrap_or(0);
+                *slot = Some((key, HipDenseOp::from_mat(*self, device)?));
+            }
+            Ok(g(&slot.as_ref().unwrap().1.handle))
+        })
+    }
+}
+
+impl HipOperand for Mat<f64> {
     fn with_hip_op<R, G: FnOnce(&HipCsrOp) -> R>(&self, g: G) -> Result<R, LanczosError> {
         self.as_ref().with_hip_op(g)
     }

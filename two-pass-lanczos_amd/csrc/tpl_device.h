@@ -190,6 +190,17 @@ struct CsrDev {
   int32_t s_win_max;
 };
 
+// Device view of a dense operator (tpl_op_create_dense; kernels: tpl_k_dense.hip): element
+// (i, j) at a[i * ld + j], ld >= n even and the base 256-B aligned; rows [0, n) are readable
+// over the whole leading dimension. S: column slices of a row (1, 2, 4 or 8). A struct of
+// its own: CsrDev and the kernel arguments of the CSR path carry nothing of it.
+struct DenseDev {
+  const double* a;
+  int64_t ld;
+  int32_t n;
+  int32_t S;
+};
+
 // The variant flag F of the SpMV-shaped kernels (k_spmv<F>, k_p1_spmv<F> and its siblings,
 // k_p2_spmv<F>; tpl_kcommon.h variant_exists): one instance per layout format.
 constexpr int kVarWidth = 7;    // mask: the uniform chunk width 1..4 (0: any per-chunk width)

@@ -116,6 +116,7 @@ tpl_status tpl_op_ftk_exp_times_batch_device(tpl_op_t op, const double* alphas,
       kmax = std::max(kmax, steps[c]);
     }
     if (kmax > kDevExpMaxK) fail(TPL_ERR_UNSUPPORTED, "k above the device f(T_k) bound");
+    refuse_dense(op, kBatchMultiSolve);
     set_device(op);
     refuse_partitioned(op, kBatchMultiSolve);
     ensure_batch(op, (int)nb, kmax);

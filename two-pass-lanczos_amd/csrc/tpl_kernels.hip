@@ -22,6 +22,8 @@
 //                       columns per launch (building blocks: tpl_kbatch.h, state: tpl_batch.h)
 //   tpl_k_batch_multi.hip  k_bp2_minit, k_bp2_coefs0, k_bp2_xacc, k_bm_deinterleave (m functions
 //                       of every column of a group: the x updates, with k_bp2_spmv run at nflush = 0)
+//   tpl_k_dense.hip     k_dense_spmv, k_dense_p1, k_dense_p2 (a dense operator's plain product,
+//                       pass-one step and pass-two step: the matrix whole, no layout)
 //   tpl_k_dist_reorth.hip  k_long_epi_p1 / _y / _p2 (partitioned solve) and k_reorth_dot /
 //                       _reduce / _update / _decide: one unit, see its header
 //   tpl_kcommon.h       device building blocks: reductions, epilogues, the sliced-ELL chunk,

@@ -9,6 +9,16 @@ namespace tpl {
 struct BatchDev;  // tpl_batch.h
 namespace launch {
 hipError_t spmv(const CsrDev& A, const double* x, double* y, hipStream_t s);
+// the dense operator's SpMV-shaped kernels (tpl_k_dense.hip): the plain product, the pass-one
+// step (A: the element geometry, G2_r norm partials) and the pass-two step, each in the place
+// of spmv / p1_spmv / p2_spmv with the same state and vectors
+hipError_t dense_spmv(const DenseDev& D, const double* x, double* y, hipStream_t s);
+hipError_t dense_p1(const DenseDev& D, const CsrDev& A, const DevState& S, const double* xsrc,
+                    const double* r_cur, const double* r_prev, double* W, double* Vcol, int j,
+                    hipStream_t s, unsigned long long* stamp = nullptr);
+hipError_t dense_p2(const DenseDev& D, const DevState& S, const double* xsrc, const double* v_cur,
+                    const double* v_prev, double* v_next, double* x, double* Vcol, int j,
+                    int nflush, hipStream_t s);
 hipError_t p1_init(const CsrDev& A, const DevState& S, const double* b, hipStream_t s);
 // stamp: workgroup 0 records the launch's start there (live timing), or nullptr
 hipError_t p1_spmv(const CsrDev& A, const DevState& S, const double* xsrc, const double* r_cur,

@@ -18,7 +18,7 @@ namespace tpl {
 // slices 13.61; at 50k: 1 slice 7.1 ms, 2 slices 9.1) — slice s runs on the XCDs
 // b % 8 == s (mod slices), so each L2 caches only its slice's columns — and, when a
 // (row, slice) piece would exceed one bin, more slices until every piece fits.
-static int auto_slices(int64_t n_cols) {
+int auto_slices(int64_t n_cols) {
   int s = 1;
   while (s < kSlices && (double)n_cols * 8.0 / s > 0.5 * 1024.0 * 1024.0) s *= 2;
   return s;

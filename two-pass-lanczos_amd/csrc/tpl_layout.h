@@ -201,6 +201,8 @@ void permute_csr(int64_t n, const std::vector<int32_t>& rp, const std::vector<in
 // in [0, n_cols) strictly ascending.
 void check_csr(int64_t n, int64_t n_cols, const int64_t* row_ptr, const int32_t* col_idx);
 
+// Column slices of the long rows of an operator of n_cols columns (the auto rule).
+int auto_slices(int64_t n_cols);
 // Element-wise workgroups of an operator of n rows (build_layout's rule): G2 blocks of E
 // rows each. Every rank of a partition can compute every other rank's count.
 void elem_geometry(int64_t n, const SchedParams& sp, int32_t& G2, int64_t& E);

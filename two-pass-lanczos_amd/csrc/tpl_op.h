@@ -181,6 +181,12 @@ struct tpl_op_s {
   double* d_pball = nullptr;        // [nranks x pb_ld] gathered norm partials (pb_ld > 0)
   int32_t* d_nch = nullptr;
   int32_t* d_halo_send = nullptr;
+  // dense operator (tpl_op_create_dense): the matrix whole on the device, row-major with the
+  // padded leading dimension dense_ld (tpl_device.h DenseDev); every row is a long row of the
+  // schedule, the layout holds no entries and bufs stays empty. false: a CSR operator
+  bool dense = false;
+  double* d_dense = nullptr;
+  int64_t dense_ld = 0;
   tpl::SchedParams sp;
   tpl::Layout lay;
   tpl::LayoutBufs bufs;
@@ -287,6 +293,17 @@ namespace tpl {
 int long_epi_blocks(const tpl_op_s* op);
 CsrDev csr_dev(const tpl_op_s* op, bool pass1 = false);
 inline void drop_graphs(tpl_op_s* op) { op->graphs.clear(); }
+// The kernels' view of a dense operator's storage under its current slice count.
+inline DenseDev dense_dev(const tpl_op_s* op) {
+  return DenseDev{op->d_dense, op->dense_ld, (int32_t)op->part.n, op->lay.nslices};
+}
+// What a dense operator does not run: refused before any device work.
+inline void refuse_dense(const tpl_op_s* op, const char* what) {
+  if (op->dense) fail(TPL_ERR_UNSUPPORTED, std::string(what) + " of a dense operator");
+}
+// Leading dimension of the dense storage: whole 128-B lines per row, an odd number of them
+// (rows a power of two apart would start on the same memory channel).
+inline int64_t dense_stride(int64_t n) { return 16 * (((n + 15) / 16) | 1); }
 
 // Device memory of an operator, accounted per allocation (tpl_op_device_bytes): the one
 // allocation path. Test hook: with TPL_TEST_ALLOC_CAP=<bytes> set (read on every call), a

@@ -186,6 +186,23 @@ Gathered gather_rule(const tpl_op_s* op) {
 // freed. The price: while both sets exist a rebuild's peak device memory is one layout's
 // worth higher (init_op's first build has no old set).
 void rebuild_schedule(tpl_op_s* op, const SchedParams& cand, int reorder) {
+  if (op->dense) {
+    // A dense operator's schedule is a rule (tpl_dense_schedule), not a build: every row a
+    // long row in the caller's order, S column slices, the element geometry of n rows. The
+    // slice count only changes the kernels' loop bounds: the state and its partial arrays
+    // (NA = n, G2) stay, the graphs hold the old count and go.
+    Layout L;
+    L.lrows.resize((size_t)op->part.n);
+    for (int64_t i = 0; i < op->part.n; ++i) L.lrows[(size_t)i] = (int32_t)i;
+    L.s_identity = 1;
+    L.nslices = cand.slices > 0 ? cand.slices : auto_slices(op->part.n);
+    elem_geometry(op->part.n, SchedParams{}, L.G2, L.E);
+    op->sp = cand;
+    op->reorder = reorder;
+    op->lay = std::move(L);
+    if (!op->plan_only) drop_graphs(op);
+    return;
+  }
   ColMap cmap;
   const RankPlan& part = op->part;
   if (part.halo) {
@@ -272,7 +289,8 @@ namespace {
 // Steps the operator's cache should hold at a state capacity of kc steps. No cache for a
 // partitioned operator (its ypart is the exchange's).
 size_t wanted_cache_rows(const tpl_op_s* op, size_t kc) {
-  if (op->dist) return 0;
+  // nor for a dense one: caching every row's sum would be the standard method's memory
+  if (op->dist || op->dense) return 0;
   return (size_t)long_cache_rows(op->long_cache, op->long_cache_budget, op->part.n,
                                  (int64_t)op->lay.lrows.size(), kc);
 }
@@ -917,6 +935,52 @@ tpl_status tpl_op_create_csr(tpl_ctx_t ctx, int64_t n, int64_t nnz, const int64_
   });
 }
 
+// The matrix whole: n rows, dense_stride(n) apart, the padding zeroed (it is never summed).
+// `a` is read during the call only.
+tpl_status tpl_op_create_dense(tpl_ctx_t ctx, int64_t n, const double* a, int64_t lda, int mem,
+                               tpl_op_t* out) {
+  return guarded([&] {
+    if (!ctx || !out || !a) fail(TPL_ERR_INVALID_ARGUMENT, "ctx/a/out is NULL");
+    if (n <= 0) fail(TPL_ERR_INVALID_ARGUMENT, "a dense operator needs n >= 1");
+    if (lda < n) fail(TPL_ERR_INVALID_ARGUMENT, "a dense operator needs lda >= n");
+    if (mem != TPL_MEM_HOST && mem != TPL_MEM_DEVICE)
+      fail(TPL_ERR_INVALID_ARGUMENT, "mem must be TPL_MEM_HOST or TPL_MEM_DEVICE");
+    if (n >= (int64_t)INT32_MAX) fail(TPL_ERR_UNSUPPORTED, "a dense operator of 2^31 rows or more");
+    RankPlan part;
+    part.n = part.n_glob = n;
+    part.nnz = n * n;
+    HIPCHK(hipSetDevice(ctx->device));
+    auto op = make_op(ctx, nullptr, std::move(part));
+    op->dense = true;
+    op->dense_ld = dense_stride(n);
+    const size_t bytes = (size_t)n * (size_t)op->dense_ld * sizeof(double);
+    dev_alloc(op.get(), &op->d_dense, bytes);  // first: the allocation a cap refuses
+    dev_zero(op.get(), op->d_dense, bytes);
+    HIPCHK(hipMemcpy2DAsync(op->d_dense, (size_t)op->dense_ld * sizeof(double), a,
+                            (size_t)lda * sizeof(double), (size_t)n * sizeof(double), (size_t)n,
+                            mem == TPL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                            op->stream));
+    init_op(op.get());  // synchronises: `a` is free again when the create returns
+    *out = op.release();
+  });
+}
+
+tpl_status tpl_dense_schedule(int64_t n, int32_t slices_req, int32_t* slices, int32_t* G2,
+                              int64_t* E) {
+  return guarded([&] {
+    if (n <= 0) fail(TPL_ERR_INVALID_ARGUMENT, "a dense operator needs n >= 1");
+    if (slices_req < 0 || slices_req > kSlices || (slices_req & (slices_req - 1)) != 0)
+      fail(TPL_ERR_INVALID_ARGUMENT,
+           "slices must be 0 (auto) or a power of two up to " + std::to_string(kSlices));
+    int32_t g2 = 0;
+    int64_t e = 0;
+    elem_geometry(n, SchedParams{}, g2, e);
+    if (slices) *slices = slices_req > 0 ? slices_req : auto_slices(n);
+    if (G2) *G2 = g2;
+    if (E) *E = e;
+  });
+}
+
 tpl_status tpl_op_destroy(tpl_op_t op) {
   return guarded([&] {
     if (!op) return;
@@ -935,7 +999,7 @@ int tpl_op_flags(tpl_op_t op) {
   return (op->dist ? 1 : 0) | (op->eager ? 2 : 0) | (op->lay.val_i8 ? 4 : 0) |
          (op->lay.s_col16 ? 8 : 0) | (op->lay.b_col16 ? 16 : 0) | (op->last_one_graph ? 32 : 0) |
          (!op->perm.empty() || op->part.local_order ? 64 : 0) | (op->pb_ld > 0 ? 128 : 0) |
-         (op->last_long_cache ? 256 : 0) | (op->last_fused_p2 ? 512 : 0);
+         (op->last_long_cache ? 256 : 0) | (op->last_fused_p2 ? 512 : 0) | (op->dense ? 1024 : 0);
 }
 
 tpl_status tpl_op_set_fused_pass_two(tpl_op_t op, int mode) {
@@ -967,6 +1031,7 @@ tpl_status tpl_op_set_long_cache(tpl_op_t op, int mode, uint64_t budget_bytes) {
   return guarded([&] {
     if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
     if (mode < 0 || mode > 2) fail(TPL_ERR_INVALID_ARGUMENT, "long-row cache mode must be 0, 1 or 2");
+    if (mode == 1) refuse_dense(op, "the long-row cache");  // auto resolves to off
     set_device(op);
     sync_checked(op);
     // the buffer itself is resized by the next solve's ensure_state
@@ -1001,6 +1066,7 @@ tpl_status tpl_op_set_reorder(tpl_op_t op, int mode) {
   return guarded([&] {
     if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
     if (mode < 0 || mode > 2) fail(TPL_ERR_INVALID_ARGUMENT, "reorder mode must be 0, 1 or 2");
+    if (mode == 1) refuse_dense(op, "the locality order");  // auto resolves to off
     reschedule(op, mode, [](SchedParams&) {});
   });
 }
@@ -1018,6 +1084,7 @@ tpl_status tpl_op_permutation(tpl_op_t op, int32_t* perm) {
 tpl_status tpl_op_set_value_format(tpl_op_t op, int compress) {
   return guarded([&] {
     if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
+    refuse_dense(op, "a value format");
     reschedule(op, op->reorder, [&](SchedParams& sp) {
       sp.compress_values = compress != 0;
       sp.compress_cols = compress != 0;
@@ -1042,6 +1109,7 @@ tpl_status tpl_op_schedule(tpl_op_t op, int32_t* n_short, int32_t* n_long, int32
 tpl_status tpl_op_set_schedule(tpl_op_t op, int32_t short_row_max, int32_t max_g2) {
   return guarded([&] {
     if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
+    refuse_dense(op, "a short-row schedule");
     reschedule(op, op->reorder, [&](SchedParams& sp) {
       if (short_row_max != 0) sp.short_row_max = short_row_max < 0 ? -1 : short_row_max;
       if (max_g2 > 0) sp.max_g2 = max_g2;
@@ -1082,6 +1150,7 @@ tpl_status tpl_op_set_order_groups(tpl_op_t op, int32_t groups) {
     if (!op) fail(TPL_ERR_INVALID_ARGUMENT, "op is NULL");
     if (groups < 0) fail(TPL_ERR_INVALID_ARGUMENT, "group count must be >= 0 (0: default 16)");
     if (op->dist) fail(TPL_ERR_UNSUPPORTED, "the locality order is single-GPU only");
+    refuse_dense(op, "the locality order");
     reschedule(op, op->reorder, [&](SchedParams& sp) {
       sp.order_groups = groups > 0 ? groups : SchedParams{}.order_groups;
     });

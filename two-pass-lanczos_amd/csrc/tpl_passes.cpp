@@ -75,6 +75,18 @@ struct P2Rot {
 inline P2Rot p2_rot(const tpl_op_s* op, int t) {
   return {op->V2G[t % 3], op->V2[t % 3], op->V2[(t + 2) % 3], op->V2[(t + 1) % 3]};
 }
+// The pass-one step's SpMV launch of step j, by the operator's storage: k_dense_p1 for a dense
+// operator, else k_p1_spmv (or its siblings) on the layout A.
+inline void launch_p1_spmv(tpl_op_s* op, const CsrDev& A, int j, double* Vcol,
+                           unsigned long long* stamp) {
+  const double* prev = j >= 2 ? r_of(op, j - 1) : nullptr;
+  if (op->dense)
+    HIPCHK(launch::dense_p1(dense_dev(op), A, op->st.S, rG_of(op, j), r_of(op, j), prev, op->W,
+                            Vcol, j, op->stream, stamp));
+  else
+    HIPCHK(launch::p1_spmv(A, op->st.S, rG_of(op, j), r_of(op, j), prev, op->W, Vcol, j,
+                           op->stream, stamp));
+}
 } // namespace
 
 bool use_graphs() {
@@ -127,8 +139,7 @@ void enqueue_p1_step(tpl_op_s* op, int j, int k, double* Vcol, bool elim, unsign
                      unsigned long long* st2, double* ycrow) {
   CsrDev A = csr_dev(op, true);
   if (ycrow && !op->dist) A.ypart = ycrow;
-  HIPCHK(launch::p1_spmv(A, op->st.S, rG_of(op, j), r_of(op, j), j >= 2 ? r_of(op, j - 1) : nullptr,
-                         op->W, Vcol, j, op->stream, st1));
+  launch_p1_spmv(op, A, j, Vcol, st1);
   if (op->dist) enqueue_p1_exchange_a(op, A);
   if (op->part.hybrid)
     HIPCHK(launch::long_epi_p1(A, op->st.S, op->d_yall, op->dist->nranks, r_of(op, j),
@@ -171,12 +182,18 @@ static void enqueue_pass2_init(tpl_op_s* op, size_t steps, double* Vout) {
 // The pass-two step launch: step record j, the buffers at position t of their rotation
 // (a sweep: t = j; the profiler re-runs one step's record as the buffers turn). The single
 // place that picks the kernel: k_p2_cached when the running tpl_lanczos_two_pass's pass one
-// stored step j's row of the long-row cache (cache_row), else the full k_p2_spmv.
+// stored step j's row of the long-row cache (cache_row), k_dense_p2 for a dense operator (it
+// keeps no cache), else the full k_p2_spmv.
 void launch_p2_step(tpl_op_s* op, const CsrDev& A, int j, int t, int nflush, double* Vcol) {
   const P2Rot v = p2_rot(op, t);
   if (const double* yc = cache_row(op, j)) {
     HIPCHK(launch::p2_cached(A, op->st.S, v.G, v.cur, j >= 2 ? v.prev : nullptr, v.next, op->x,
                              Vcol, yc, op->st.d_ylrow, j, nflush, op->stream));
+    return;
+  }
+  if (op->dense) {
+    HIPCHK(launch::dense_p2(dense_dev(op), op->st.S, v.G, v.cur, j >= 2 ? v.prev : nullptr, v.next,
+                            op->x, Vcol, j, nflush, op->stream));
     return;
   }
   HIPCHK(launch::p2_spmv(A, op->st.S, v.G, v.cur, j >= 2 ? v.prev : nullptr, v.next, op->x, Vcol,
@@ -404,9 +421,7 @@ void run_two_pass_shifted_inv_tol(tpl_op_s* op, size_t kmax, const launch::Shift
     for (int j = 1; j <= (int)kmax; ++j) {
       CsrDev A = csr_dev(op, true);
       if (double* ycrow = ck ? cache_row(op, j) : nullptr) A.ypart = ycrow;
-      HIPCHK(launch::p1_spmv(A, op->st.S, rG_of(op, j), r_of(op, j),
-                             j >= 2 ? r_of(op, j - 1) : nullptr, op->W, nullptr, j, op->stream,
-                             nullptr));
+      launch_p1_spmv(op, A, j, nullptr, nullptr);
       HIPCHK(launch::p1_axpy_stol(A, op->st.S, op->W, r_of(op, j), op->R[(j + 1) % 3], j,
                                   (int)kmax, t, op->stream));
     }
@@ -680,9 +695,7 @@ void run_two_pass_inv_tol(tpl_op_s* op, size_t kmax) {
     for (int j = 1; j <= (int)kmax; ++j) {
       CsrDev A = csr_dev(op, true);
       if (double* ycrow = ck ? cache_row(op, j) : nullptr) A.ypart = ycrow;
-      HIPCHK(launch::p1_spmv(A, op->st.S, rG_of(op, j), r_of(op, j),
-                             j >= 2 ? r_of(op, j - 1) : nullptr, op->W, nullptr, j, op->stream,
-                             nullptr));
+      launch_p1_spmv(op, A, j, nullptr, nullptr);
       HIPCHK(launch::p1_axpy_tol(A, op->st.S, op->W, r_of(op, j), op->R[(j + 1) % 3], j,
                                  (int)kmax, op->d_tol, op->stream));
     }

@@ -13,7 +13,9 @@ double tpl_kernel_algo_bytes(tpl_op_t op, int kernel) {
   // epilogue vectors they must touch (DESIGN.md "Algorithmic bytes").
   if (!op) return 0.0;
   const double n = (double)op->part.n, nnz = (double)op->part.nnz;
-  const double spmv = 12.0 * nnz + 4.0 * (n + 1.0) + 16.0 * n;
+  // a dense operator: the stored matrix, padding included, x read once, y written once
+  const double spmv = op->dense ? 8.0 * n * (double)op->dense_ld + 16.0 * n
+                                : 12.0 * nnz + 4.0 * (n + 1.0) + 16.0 * n;
   switch (kernel) {
     case TPL_KERNEL_SPMV: return spmv;
     case TPL_KERNEL_PASS1_SPMV: return spmv + 8.0 * n;   // + r_{j-1} read (w is the y write)
@@ -92,6 +94,7 @@ tpl_status tpl_profile_kernel(tpl_op_t op, int kernel, int iters, double* avg_us
                               double* algo_bytes) {
   return guarded([&] {
     if (!op || !avg_us || iters <= 0) fail(TPL_ERR_INVALID_ARGUMENT, "bad argument");
+    refuse_dense(op, "the per-kernel profiler");
     set_device(op);
     if (op->st.kcap < 4) ensure_state(op, 4);
     const DevState& S = op->st.S;
@@ -181,6 +184,7 @@ tpl_status tpl_op_tune_order(tpl_op_t op, const int32_t* groups, int32_t count, 
     if (!op || count < 0 || (count > 0 && !groups) || iters <= 0)
       fail(TPL_ERR_INVALID_ARGUMENT, "bad argument");
     if (op->dist) fail(TPL_ERR_UNSUPPORTED, "the locality order is single-GPU only");
+    refuse_dense(op, "the locality order");
     set_device(op);
     sync_checked(op);
     static const int32_t kDefault[] = {12, 13, 14, 15, 16, 17, 18, 19, 20, 22, 24};

@@ -61,10 +61,12 @@ inline void check_multi(tpl_op_s* op, bool have_args, size_t m) {
   need(op && have_args), check_m(m), set_device(op), refuse_partitioned(op, kMultiSolve);
 }
 inline void check_batch_args(tpl_op_s* op, bool have_args, size_t s) {
-  need(op && have_args), check_s(s), set_device(op), refuse_partitioned(op, kBatchSolve);
+  need(op && have_args), refuse_dense(op, kBatchSolve);
+  check_s(s), set_device(op), refuse_partitioned(op, kBatchSolve);
 }
 inline void check_batch_multi_args(tpl_op_s* op, bool have_args, size_t s, size_t m) {
-  need(op && have_args), check_s(s), check_m(m), set_device(op);
+  need(op && have_args), refuse_dense(op, kBatchMultiSolve);
+  check_s(s), check_m(m), set_device(op);
   refuse_partitioned(op, kBatchMultiSolve);
 }
 void check_k(size_t k);

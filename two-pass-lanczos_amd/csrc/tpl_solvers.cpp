@@ -192,7 +192,10 @@ tpl_status tpl_op_apply(tpl_op_t op, const double* x, double* y, int mem) {
       gather_vec(op, op->tmpG);
     }
     const CsrDev A = csr_dev(op);
-    HIPCHK(launch::spmv(A, op->tmpG, op->W, op->stream));
+    if (op->dense)
+      HIPCHK(launch::dense_spmv(dense_dev(op), op->tmpG, op->W, op->stream));
+    else
+      HIPCHK(launch::spmv(A, op->tmpG, op->W, op->stream));
     if (op->part.hybrid && A.n_long > 0) {
       dist_allgather(op, op->d_yall, (size_t)A.y_ld);
       HIPCHK(launch::long_epi_y(A, op->d_yall, op->dist->nranks, op->W, op->stream));

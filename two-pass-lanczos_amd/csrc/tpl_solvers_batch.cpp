@@ -486,6 +486,7 @@ tpl_status tpl_lanczos_two_pass_batch_shifted_inv_tol(
   return guarded([&] {
     need(op && B && sigmas && x_out), check_s(s), check_m(m), check_tol(tol);
     check_finite(sigmas, m, kShiftsFinite);
+    refuse_dense(op, kBatchMultiSolve);
     set_device(op);
     refuse_partitioned(op, kBatchMultiSolve);
     check_b(op, B, b_len), check_k(kmax);
@@ -541,6 +542,7 @@ tpl_status tpl_lanczos_pass_two_batch_multi_cut(tpl_op_t op, const double* B, in
       check_b_norm(b_norms[c]);
       if (steps[c] > 1 && !betas) fail_short_decomp();
     }
+    refuse_dense(op, kBatchMultiSolve);
     set_device(op);
     refuse_partitioned(op, kBatchMultiSolve);
     check_b(op, B, b_len);

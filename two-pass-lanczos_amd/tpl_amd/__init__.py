@@ -12,7 +12,7 @@ src/lib.rs:94-101) on top of the C ABI of libtpl_amd.so (include/tpl.h):
 from . import _lib
 from . import algorithms, error, ftk, solvers
 from .error import DataLoaderError, LanczosError, LanczosErrorKind, TplError
-from .operator import HipCsrOp, HostPlan, device_count, locality_order, refresh_uploaded
+from .operator import HipCsrOp, HipDenseOp, HostPlan, device_count, locality_order, refresh_uploaded
 from .operator import (LONG_CACHE_TWO_PASS, LONG_CACHE_TWO_PASS_BATCH,
                        LONG_CACHE_TWO_PASS_BATCH_MULTI, LONG_CACHE_TWO_PASS_MULTI)
 from .solvers import (lanczos, lanczos_multi, lanczos_two_pass, lanczos_two_pass_batch,
@@ -25,7 +25,7 @@ __version__ = "0.1.0"
 LIB_PATH = _lib.LIB_PATH
 
 __all__ = [
-    "lanczos", "lanczos_two_pass", "lanczos_multi", "lanczos_two_pass_multi", "lanczos_two_pass_batch", "lanczos_two_pass_batch_multi", "lanczos_two_pass_exp_times", "lanczos_two_pass_batch_exp_times", "lanczos_two_pass_inv_tol", "lanczos_two_pass_shifted_inv_tol", "lanczos_two_pass_batch_shifted_inv_tol", "algorithms", "solvers", "error", "ftk", "HipCsrOp",
+    "lanczos", "lanczos_two_pass", "lanczos_multi", "lanczos_two_pass_multi", "lanczos_two_pass_batch", "lanczos_two_pass_batch_multi", "lanczos_two_pass_exp_times", "lanczos_two_pass_batch_exp_times", "lanczos_two_pass_inv_tol", "lanczos_two_pass_shifted_inv_tol", "lanczos_two_pass_batch_shifted_inv_tol", "algorithms", "solvers", "error", "ftk", "HipCsrOp", "HipDenseOp",
     "LanczosError", "LanczosErrorKind", "TplError", "DataLoaderError", "device_count",
     "locality_order", "HostPlan", "refresh_uploaded",
     "LONG_CACHE_TWO_PASS", "LONG_CACHE_TWO_PASS_MULTI", "LONG_CACHE_TWO_PASS_BATCH",

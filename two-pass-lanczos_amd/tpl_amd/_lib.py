@@ -85,6 +85,10 @@ tpl_ctx_destroy = _sig("tpl_ctx_destroy", c_int, c_void_p)
 tpl_ctx_synchronize = _sig("tpl_ctx_synchronize", c_int, c_void_p)
 tpl_op_create_csr = _sig("tpl_op_create_csr", c_int, c_void_p, c_int64, c_int64,
                          POINTER(c_int64), POINTER(c_int32), PD, POINTER(c_void_p))
+tpl_op_create_dense = _sig("tpl_op_create_dense", c_int, c_void_p, c_int64, c_void_p, c_int64,
+                           c_int, POINTER(c_void_p))
+tpl_dense_schedule = _sig("tpl_dense_schedule", c_int, c_int64, c_int32, POINTER(c_int32),
+                          POINTER(c_int32), POINTER(c_int64))
 tpl_op_destroy = _sig("tpl_op_destroy", c_int, c_void_p)
 tpl_op_nrows = _sig("tpl_op_nrows", c_int64, c_void_p)
 tpl_op_nnz = _sig("tpl_op_nnz", c_int64, c_void_p)
@@ -309,3 +313,4 @@ tpl_lanczos_pass_two_batch_multi_cut = _sig(
 tpl_batch_shifted_inv_tol_auto_k = _sig("tpl_batch_shifted_inv_tol_auto_k", c_size_t)
 EXPORTED += ["tpl_lanczos_two_pass_batch_shifted_inv_tol", "tpl_lanczos_pass_two_batch_multi_cut",
              "tpl_batch_shifted_inv_tol_auto_k"]
+EXPORTED += ["tpl_op_create_dense", "tpl_dense_schedule"]

@@ -7,11 +7,14 @@ reference's binaries, with the same inputs, sweeps and CSV schemas:
                                          relative_solution_deviation      (diagonal spectra)
   orthogonality src/bin/orthogonality.rs k,ortho_loss_standard,ortho_loss_regenerated,
                                          basis_drift_fro,solution_deviation_l2
+  dense-tradeoff src/bin/dense_tradeoff.rs variant,k,time_s,rss_kb           (dense R + R^T, f = inv)
 
     python -m tpl_amd.harness tradeoff --arcs 500000 --output tradeoff.csv
     python -m tpl_amd.harness accuracy --function inv --scenario well-conditioned --output a.csv
+    python -m tpl_amd.harness dense-tradeoff --n 10000 --k-start 100 --k-end 1000 --k-step 100 \
+        --output dense.csv
 
-tradeoff / scalability follow the reference's orchestrator (src/bin/tradeoff.rs:160-214,
+tradeoff / scalability / dense-tradeoff follow the reference's orchestrator (src/bin/tradeoff.rs:160-214,
 src/bin/scalability.rs:120-215): every variant runs in a FRESH worker process (this
 module re-run with TPL_HARNESS_VARIANT set) that prints its CSV rows, so one variant's
 allocations never show in the other's numbers. Per k the worker first makes one
@@ -41,7 +44,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import algorithms, solvers
-from .operator import HipCsrOp
+from .operator import HipCsrOp, HipDenseOp
 from .utils.data_loader import generate_kkt, load_kkt_system, write_qfc_3line
 from .utils.rng import std_rng_f64
 
@@ -106,6 +109,29 @@ def tradeoff_worker(variant, a, b, ks, device: int = 0):
     return rows
 
 
+def dense_instance(n: int):
+    """The dense study's operator and b (src/bin/dense_tradeoff.rs:155-162): A = R + R^T with
+    R = Mat::from_fn(n, n, |_, _| rng.random()) after StdRng::seed_from_u64(42), and
+    b = A (1/sqrt(n)) 1. Fill order: this assumes from_fn calls its closure column by column
+    (faer's column-major storage order), i.e. draw number j n + i lands at R[i, j]; A is
+    R + R^T, so the other order gives the same matrix — transposing R only swaps the two terms."""
+    r = std_rng_f64(n * n, 42).reshape(n, n).T
+    a = r + r.T
+    return a, a @ np.full(n, 1.0 / np.sqrt(n))
+
+
+def dense_tradeoff_worker(variant, a, b, ks, device: int = 0):
+    """Rows (variant, k, time_s, rss_kb) of ONE variant, k ascending
+    (src/bin/dense_tradeoff.rs:150-219, run_worker)."""
+    op = HipDenseOp(a, device=device)
+    rows = []
+    for k in ks:
+        t, rss, _ = _timed(variant, op, b, k)
+        rows.append({"variant": variant, "k": k, "time_s": t, "rss_kb": rss})
+    op.close()
+    return rows
+
+
 def scalability_worker(variant, instances, k: int = 500, device: int = 0):
     """Rows (variant, n, k, time_s, rss_kb, device_kb) of ONE variant over the instances."""
     rows = []
@@ -134,6 +160,7 @@ def run_workers(argv, fields):
 
 
 TRADEOFF_FIELDS = ["variant", "k", "time_s", "rss_kb", "device_kb"]
+DENSE_TRADEOFF_FIELDS = ["variant", "k", "time_s", "rss_kb"]
 SCALABILITY_FIELDS = ["variant", "n", "k", "time_s", "rss_kb", "device_kb"]
 
 
@@ -222,6 +249,12 @@ def main(argv=None):
     t.add_argument("--k-end", type=int, default=1000)
     t.add_argument("--k-step", type=int, default=50)
     t.add_argument("--output", required=True)
+    dt = sub.add_parser("dense-tradeoff")
+    dt.add_argument("--n", type=int, default=10000)
+    dt.add_argument("--k-start", type=int, default=50)
+    dt.add_argument("--k-end", type=int, default=1000)
+    dt.add_argument("--k-step", type=int, default=50)
+    dt.add_argument("--output", required=True)
     s = sub.add_parser("scalability")
     s.add_argument("--arcs", type=int, nargs="+", default=[5000, 50000, 500000])
     s.add_argument("--k", type=int, default=500)
@@ -239,8 +272,12 @@ def main(argv=None):
     a = p.parse_args(argv)
     argv = list(sys.argv[1:] if argv is None else argv)
     worker = os.environ.get(VARIANT_ENV)
-    if a.cmd in ("tradeoff", "scalability") and worker:
-        if a.cmd == "tradeoff":
+    if a.cmd in ("tradeoff", "scalability", "dense-tradeoff") and worker:
+        if a.cmd == "dense-tradeoff":
+            A, b = dense_instance(a.n)
+            rows = dense_tradeoff_worker(worker, A, b,
+                                         list(range(a.k_start, a.k_end + 1, a.k_step)))
+        elif a.cmd == "tradeoff":
             A, b = kkt_instance(a.arcs, a.dmx, a.qfc, fixtures)
             rows = tradeoff_worker(worker, A, b, list(range(a.k_start, a.k_end + 1, a.k_step)))
         else:
@@ -252,6 +289,8 @@ def main(argv=None):
         return
     if a.cmd == "tradeoff":
         rows = run_workers(argv, TRADEOFF_FIELDS)
+    elif a.cmd == "dense-tradeoff":
+        rows = run_workers(argv, DENSE_TRADEOFF_FIELDS)
     elif a.cmd == "scalability":
         rows = run_workers(argv, SCALABILITY_FIELDS)
     elif a.cmd == "accuracy":

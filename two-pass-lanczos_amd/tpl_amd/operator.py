@@ -146,24 +146,11 @@ class HostPlan:
             pass
 
 
-class HipCsrOp:
-    """Symmetric sparse operator resident in the HBM of one MI355X.
-
-    Mirrors ``LinOp``: ``nrows()``, ``ncols()``, ``apply(x)``.
-    """
-
-    def __init__(self, a, device: int = 0):
-        n, rp, ci, v = _as_csr_arrays(a)
-        self.device = device
-        self._ctx = context(device)
-        h = c_void_p()
-        check(_lib.tpl_op_create_csr(
-            self._ctx, n, int(rp[-1]) if n > 0 else 0,
-            rp.ctypes.data_as(POINTER(c_int64)), ci.ctypes.data_as(POINTER(c_int32)),
-            v.ctypes.data_as(POINTER(c_double)), byref(h)))
-        self._op = h.value
-        self._n = n
-        self._nnz = int(rp[-1]) if n > 0 else 0
+class _HipOp:
+    """What every operator resident in the HBM of one MI355X shares, whatever its storage
+    (``HipCsrOp``, ``HipDenseOp``): the ``LinOp`` surface and the schedule, measurement and
+    solver-mode methods, all through the handle's C ABI calls. Subclasses create ``_op`` and
+    set ``_n``, ``_nnz`` and ``device``."""
 
     # -- LinOp surface -------------------------------------------------------
     def nrows(self) -> int:
@@ -426,8 +413,80 @@ class HipCsrOp:
         except Exception:
             pass
 
+
+class HipCsrOp(_HipOp):
+    """Symmetric sparse operator resident in the HBM of one MI355X.
+
+    Mirrors ``LinOp``: ``nrows()``, ``ncols()``, ``apply(x)``.
+    """
+
+    def __init__(self, a, device: int = 0):
+        n, rp, ci, v = _as_csr_arrays(a)
+        self.device = device
+        self._ctx = context(device)
+        h = c_void_p()
+        check(_lib.tpl_op_create_csr(
+            self._ctx, n, int(rp[-1]) if n > 0 else 0,
+            rp.ctypes.data_as(POINTER(c_int64)), ci.ctypes.data_as(POINTER(c_int32)),
+            v.ctypes.data_as(POINTER(c_double)), byref(h)))
+        self._op = h.value
+        self._n = n
+        self._nnz = int(rp[-1]) if n > 0 else 0
+
     def __repr__(self):
         return f"HipCsrOp(n={self._n}, nnz={self._nnz}, device={self.device})"
+
+
+class HipDenseOp(_HipOp):
+    """Dense symmetric operator resident in the HBM of one MI355X — faer's ``LinOp<f64>`` for
+    a dense ``Mat<f64>`` (the reference's tests/correctness.rs and src/bin/dense_tradeoff.rs).
+
+    ``a``: a square numpy array (any strides; copied to a C-contiguous float64 array when it
+    is not one) or a 2-D torch CUDA float64 tensor (read in place, its row stride as lda).
+    A must be symmetric (not checked), so row- and column-major storage are the same thing.
+    The device keeps the matrix whole and streams it once per step; every row is a long row
+    of the canonical order over all n columns (``schedule()``), so ``oracle.Operator`` on the
+    full CSR of ``a`` with that schedule reproduces every result bit for bit.
+    """
+
+    def __init__(self, a, device: int = 0):
+        self.device = device
+        if _is_torch_cuda(a):
+            import torch
+            if a.dim() != 2 or a.shape[0] != a.shape[1]:
+                raise TplError(_lib.TPL_ERR_INVALID_ARGUMENT, "operator must be square")
+            if a.dtype != torch.float64 or a.stride(1) != 1 or a.stride(0) < a.shape[1]:
+                a = a.to(torch.float64).contiguous()
+            torch.cuda.synchronize(a.device)
+            n, ptr, lda, mem = int(a.shape[0]), a.data_ptr(), int(a.stride(0)), _lib.TPL_MEM_DEVICE
+        else:
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim != 2 or a.shape[0] != a.shape[1]:
+                raise TplError(_lib.TPL_ERR_INVALID_ARGUMENT, "operator must be square")
+            es = a.itemsize
+            if a.shape[0] > 1 and not (a.strides[1] == es and a.strides[0] % es == 0
+                                       and a.strides[0] >= a.shape[1] * es):
+                a = np.ascontiguousarray(a)  # a row-major view with lda >= n is read in place
+            n, ptr, mem = int(a.shape[0]), a.ctypes.data, _lib.TPL_MEM_HOST
+            lda = a.strides[0] // es if n > 1 else max(n, 1)
+        self._ctx = context(device)
+        h = c_void_p()
+        check(_lib.tpl_op_create_dense(self._ctx, n, ptr, lda, mem, byref(h)))
+        self._op = h.value
+        self._n = n
+        self._nnz = n * n
+
+    def __repr__(self):
+        return f"HipDenseOp(n={self._n}, device={self.device})"
+
+
+def dense_schedule(n: int, slices: int = 0):
+    """tpl_dense_schedule (host only): the schedule a HipDenseOp of n rows reports, as the
+    dict ``HipDenseOp.schedule()`` returns."""
+    sl, g2, e = c_int32(), c_int32(), c_int64()
+    check(_lib.tpl_dense_schedule(int(n), int(slices), byref(sl), byref(g2), byref(e)))
+    return {"short_rows": np.zeros(0, dtype=np.int32), "long_rows": np.arange(n, dtype=np.int32),
+            "G2": g2.value, "E": e.value, "slices": sl.value, "perm": None}
 
 
 HostPlan.schedule = HipCsrOp.schedule
@@ -462,17 +521,18 @@ def _upload(a, device: int) -> "HipCsrOp":
     return HipCsrOp(a, device=device)
 
 
-def as_operator(operator, device: int = 0) -> "HipCsrOp":
-    """A solver's `operator`: a HipCsrOp as is (the zero-overhead form), or a scipy sparse
+def as_operator(operator, device: int = 0) -> "_HipOp":
+    """A solver's `operator`: a HipCsrOp or HipDenseOp as is (the zero-overhead form), or a scipy sparse
     matrix uploaded on first use and re-used on this thread while its operand key is
     unchanged (the Rust shim's `HipOperand for SparseColMatRef` rule,
     integration/rust/hip.rs). After changing a matrix's values IN PLACE call
     ``refresh_uploaded()``: the key sees new arrays, sizes and sampled words, not every word."""
-    if isinstance(operator, HipCsrOp):
+    if isinstance(operator, _HipOp):
         return operator
     import scipy.sparse as sp
     if not sp.issparse(operator) or operator.format not in ("csr", "csc"):
-        raise TypeError("operator must be a tpl_amd.HipCsrOp or a scipy CSR / CSC matrix")
+        raise TypeError("operator must be a tpl_amd.HipCsrOp, a tpl_amd.HipDenseOp or a scipy CSR / CSC "
+                        "matrix")
     key = operand_key(operator)
     slot = getattr(_uploaded, "slot", None)
     if slot is None or slot[0] != key:
