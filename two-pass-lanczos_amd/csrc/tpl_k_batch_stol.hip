@@ -14,53 +14,31 @@
 // The y of every (c, i) is k_ftk_inv_shifts as it stands, one launch per column on column
 // c's view of the group state (tpl_passes.cpp).
 //
-// Words 5, 6 and 7 of a column's eight flags (BatchDev::flags + 8 c) play the roles of
-// DevState::flags[5], [kFlagHit] and [kFlagRes]; no other batch kernel reads or writes them
-// and k_bp1_init zeroes them with the rest.
+// Words 5, 6 and 7 of a column's eight flags (BatchDev::flags + 8 c) are the stop's
+// kFlagDone, kFlagHit and kFlagRes (tpl_kstop.h).
 //
-// k_bp1_axpy_stol repeats k_bp1_axpy's text (tpl_k_batch_p1.hip): the existing instances must
-// keep their instructions. The additions are marked "stol:". A change to k_bp1_axpy's element
-// part belongs here too.
+// Shared (tpl_kstop.h) with the one-column solve (tpl_k_p1_stol.hip): those words, the rule
+// and the vote of the stop, the elimination lane (stol_elim_wave) and the fin wave
+// (stol_fin_wave); a column's view of the group's per-shift state is
+// launch::BatchShiftTol::col, on the host and here.
+// Still repeated: k_bp1_axpy_stol's element part is k_bp1_axpy's text (tpl_k_batch_p1.hip),
+// as k_p1_axpy_tol's is k_p1_axpy's (tpl_k_p1_tol.hip gives the reason): the existing
+// instances must keep their instructions. The additions are marked "stol:". A change to
+// k_bp1_axpy's element part belongs here too.
 #include "../../include/tpl.h"
 #include "tpl_kbatch.h"
-#include "tpl_klu.h"
+#include "tpl_kstop.h"
 #include "tpl_launch.h"
 
 namespace tpl {
 
-// As tpl_k_p1_stol.hip's (its comments hold): the flag words of the stop, the rule by which
-// every element block of a launch decides alike, and the wave's vote.
-constexpr int kBFlagDone = 5, kBFlagHit = 6, kBFlagRes = 7;
-__device__ __forceinline__ bool b_hit_before(int hit, int j) {
-  return hit != 0 && j > (hit + 1 > 3 ? hit + 1 : 3);
-}
-__device__ __forceinline__ int b_wave_hits(int hit, bool& every) {
-  every = __ballot(hit != 0) == ~0ull;
-  int mx = hit;
-  for (int o = 32; o > 0; o >>= 1) {
-    const int other = __shfl_xor(mx, o);
-    mx = other > mx ? other : mx;
-  }
-  return mx;
-}
-// Column c's block of the group's per-shift state (launch::BatchShiftTol::col on the device).
-__device__ __forceinline__ launch::ShiftTol b_col_view(const launch::BatchShiftTol& t, int c) {
-  launch::ShiftTol v = t.t0;
-  v.st += (size_t)c * t.dstride;
-  v.lu += (size_t)c * t.dstride;
-  v.res += (size_t)c * t.dstride;
-  v.hits += (size_t)c * t.istride;
-  v.nres += (size_t)c * t.istride;
-  return v;
-}
-
 // k_bp1_axpy with NB waves of elimination lanes in one more workgroup (blockIdx.x ==
-// elim_block, the block after the element grid). Lane (c, i), i < t.m, runs lu_row on
-// (alphas_c + sig[i], betas_c) into column c's block: k_p1_axpy_stol's lane, statement for
-// statement. When every lane of wave c has stopped, its lane 0 writes M_c = max_i m*_{c,i}
-// into column c's word 6; from launch max(M_c + 1, 3) + 1 on the element blocks count column
-// c as stopped (flags[8c] = 1, flags[8c + 2] = M_c) and store nothing for it. No LDS and no
-// barrier between the waves: a column's lanes read and write that column's state only.
+// elim_block, the block after the element grid). Wave c runs stol_elim_wave on column c's
+// alphas, betas, flags and block of the per-shift state. When every lane of wave c has
+// stopped, its lane 0 writes M_c = max_i m*_{c,i} into column c's kFlagHit; from launch
+// max(M_c + 1, 3) + 1 on the element blocks count column c as stopped (flags[8c] = 1,
+// flags[8c + 2] = M_c) and store nothing for it. No LDS and no barrier between the waves: a
+// column's lanes read and write that column's state only.
 template <int NB>
 __global__ __launch_bounds__(kTPB) void k_bp1_axpy_stol(CsrDev A, BatchDev B,
                                                         const double* __restrict__ W,
@@ -71,48 +49,8 @@ __global__ __launch_bounds__(kTPB) void k_bp1_axpy_stol(CsrDev A, BatchDev B,
   if ((int)blockIdx.x == elim_block) {  // stol: the elimination workgroup
     const int c = threadIdx.x >> 6;
     if (c >= NB || j < 3) return;
-    const int i = j - 3;
-    const int s = threadIdx.x & 63, m = bt.t0.m;
-    const bool lane = s < m;
-    const launch::ShiftTol t = b_col_view(bt, c);
-    int32_t* fl = B.flags + 8 * c;
-    const double* al = B.alphas + (size_t)c * B.kcap;
-    const double* be = B.betas + (size_t)c * B.kcap;
-    const size_t am = (size_t)t.kcap * (size_t)m;  // one array of t.lu
-    const int stop = fl[0], done = fl[kBFlagDone];
-    const int every_hit = fl[kBFlagHit];  // M_c, written by an earlier launch
-    if (stop || done != i) return;  // breakdown at this step: k_ftk_inv_shifts finishes the rows
-    if (every_hit) return;          // every running row stays where its lane stopped
-    int hit = lane ? t.hits[s] : 1;
-    if (lane && !hit) {
-      const double tol = t.tol[0], sg = t.sig[s];
-      const double dli = be[i], d1 = al[i + 1] + sg, du1 = be[i + 1];
-      LuRow cur{t.st[s], t.st[m + s], t.st[2 * m + s]};
-      double* D = t.lu + s;
-      if (i == 0) {
-        cur = LuRow{al[0] + sg, dli, 1.0};
-        const double r0 = fabs(dli * (cur.b / cur.d));  // the one-step iterate
-        t.res[s] = r0;
-        if (r0 <= tol) hit = 1;
-      }
-      lu_row(i * m, true, dli, d1, du1, cur, D, D + am, D + 2 * am, D + 3 * am);
-      t.st[s] = cur.d;
-      t.st[m + s] = cur.du;
-      t.st[2 * m + s] = cur.b;
-      // the (i + 2)-step iterate. A zero pivot gives inf or NaN, never <= a finite tol
-      const double r1 = fabs(du1 * (cur.b / cur.d));
-      t.res[(size_t)(i + 1) * m + s] = r1;
-      if (!hit && r1 <= tol) hit = i + 2;
-      if (hit) t.hits[s] = hit;
-      t.nres[s] = i + 2;
-    }
-    bool every;
-    const int mx = b_wave_hits(hit, every);
-    if (s == 0) {
-      fl[kBFlagDone] = i + 1;
-      fl[kBFlagRes] = i + 2;
-      if (every) fl[kBFlagHit] = mx;
-    }
+    stol_elim_wave(bt.col(c), threadIdx.x & 63, j, B.flags + 8 * c,
+                   B.alphas + (size_t)c * B.kcap, B.betas + (size_t)c * B.kcap);
     return;
   }
   const int rb = elem_block(A.G2, blockIdx.x);
@@ -124,13 +62,13 @@ __global__ __launch_bounds__(kTPB) void k_bp1_axpy_stol(CsrDev A, BatchDev B,
 #pragma unroll
   for (int c = 0; c < NB; ++c) {
     stop[c] = B.flags[8 * c];
-    hit[c] = B.flags[8 * c + kBFlagHit];  // stol: M_c; the stop flag's 32-byte line
+    hit[c] = B.flags[8 * c + kFlagHit];  // stol: M_c; the stop flag's 32-byte line
     normj[c] = B.norms[(size_t)c * (B.kcap + 1) + j - 1];
   }
   // stol: ahead of the stop test, so that a breakdown in the step after the hit keeps M_c
 #pragma unroll
   for (int c = 0; c < NB; ++c) {
-    if (b_hit_before(hit[c], j)) {
+    if (hit_before(hit[c], j)) {
       if (rb == 0 && threadIdx.x == 0) {
         B.flags[8 * c] = 1;
         B.flags[8 * c + 2] = hit[c];
@@ -190,40 +128,16 @@ __global__ __launch_bounds__(kTPB) void k_bp1_axpy_stol(CsrDev A, BatchDev B,
       if (!stop[c]) B.Pb[(size_t)c * B.g2_ld + rb] = acc[c];
 }
 
-// After the last step launch, one wave per column (k_p1_stol_fin per column). A column whose
-// pass took two steps (kmax = 2, or a breakdown at step 3) never had its elimination wave
-// run: lane i forms its one residual by the same expression. And when the last launch's stops
-// made every lane of a column stop (or this kernel's own just did), steps_c becomes M_c here.
+// After the last step launch, one wave per column: stol_fin_wave (tpl_kstop.h) on column c
+// unless its b was zero; steps_c becomes M_c there.
 template <int NB>
 __global__ void k_bp1_stol_fin(BatchDev B, launch::BatchShiftTol bt) {
   const int c = threadIdx.x >> 6;
   if (blockIdx.x != 0 || c >= NB) return;
   int32_t* fl = B.flags + 8 * c;
   if (fl[1]) return;
-  const launch::ShiftTol t = b_col_view(bt, c);
-  const int s = threadIdx.x & 63;
-  const bool lane = s < t.m;
-  int hit = lane ? t.hits[s] : 1;
-  if (fl[kBFlagHit] == 0 && fl[2] == 2 && fl[kBFlagRes] == 0) {
-    if (lane) {
-      const double r0 = fabs(B.betas[(size_t)c * B.kcap] *
-                             (1.0 / (B.alphas[(size_t)c * B.kcap] + t.sig[s])));
-      t.res[s] = r0;
-      t.nres[s] = 1;
-      if (r0 <= t.tol[0]) {
-        hit = 1;
-        t.hits[s] = 1;
-      }
-    }
-    if (s == 0) fl[kBFlagRes] = 1;
-  }
-  bool every;
-  const int mx = b_wave_hits(hit, every);
-  if (s == 0 && every) {
-    fl[kBFlagHit] = mx;
-    fl[0] = 1;
-    fl[2] = mx;
-  }
+  stol_fin_wave(bt.col(c), threadIdx.x & 63, fl, B.alphas + (size_t)c * B.kcap,
+                B.betas + (size_t)c * B.kcap);
 }
 
 // k_bp2_xacc with a cut per (function, column): after step j, of the last nflush (1..3)

@@ -13,49 +13,27 @@
 // Every entry of a shifted tridiagonal is alphas[j] + sigma_s, one IEEE addition, here as on
 // the host (tpl_solvers.cpp shifted_col); nothing else ever forms it.
 //
-// k_p1_axpy_stol repeats k_p1_axpy_tol's text (tpl_k_p1_tol.hip), which repeats k_p1_axpy's
-// (tpl_kernels.hip), for the reason given there: the existing instances must keep their
-// instructions. The additions are marked "stol:". A change to k_p1_axpy's element part
-// belongs here too. k_ftk_inv_shifts repeats k_ftk_inv's text with div_rn and its range test
-// (tpl_kernels.hip, whose bytes the committed headline profile is tied to, stays as it is).
+// Shared (tpl_kstop.h), written once for this unit and the batch solve's
+// (tpl_k_batch_stol.hip): the flag words and rule of the stop, the wave's vote, the
+// elimination lane (stol_elim_wave), the fin wave (stol_fin_wave), and div_rn with its range
+// test, which k_ftk_inv (tpl_kernels.hip) takes from there too.
+// Still repeated: k_p1_axpy_stol's element part is k_p1_axpy_tol's text (tpl_k_p1_tol.hip),
+// which repeats k_p1_axpy's (tpl_kernels.hip), for the reason given there: one function
+// inlined into both moves instructions of the existing instances. The additions are marked
+// "stol:". A change to k_p1_axpy's element part belongs here too. k_ftk_inv_shifts repeats
+// k_ftk_inv's text: with only the back substitution as one function inlined into both, 106
+// lines of k_ftk_inv's assembly changed, and tpl_kernels.hip's bytes are the ones the
+// committed headline profile is tied to.
 #include "../../include/tpl.h"
 #include "tpl_klaunch.h"
 #include "tpl_klu.h"
+#include "tpl_kstop.h"
 
 namespace tpl {
 
-// DevState::flags words of the stop, as in tpl_k_p1_tol.hip: [kFlagHit] M = the largest
-// m*_s once EVERY shift has met the tolerance, 0 until then; [kFlagRes] the residual entries
-// formed so far by the lanes still running.
-constexpr int kFlagHit = 6;
-constexpr int kFlagRes = 7;
-// tpl_k_p1_tol.hip's rule with M: the last lane to stop is the one with the largest m*, so
-// M is written by launch M + 1 (M = 1 and 2: by launch 3), and an element block of launch j
-// acts on it only when an earlier launch wrote it — whichever value a block of launch M + 1
-// sees, every block decides alike.
-__device__ __forceinline__ bool hit_before(int hit, int j) {
-  return hit != 0 && j > (hit + 1 > 3 ? hit + 1 : 3);
-}
-// All 64 lanes of the wave call this. every: each lane's `hit` is non-zero; the return
-// value: the largest hit of the wave.
-__device__ __forceinline__ int wave_hits(int hit, bool& every) {
-  every = __ballot(hit != 0) == ~0ull;
-  int mx = hit;
-  for (int o = 32; o > 0; o >>= 1) {
-    const int other = __shfl_xor(mx, o);
-    mx = other > mx ? other : mx;
-  }
-  return mx;
-}
-
-// k_p1_axpy_tol with m lanes in the elimination workgroup's first wave. Lane s < t.m runs
-// lu_row on (alphas + sig[s], betas): its rows go to t.lu, its running row to t.st, its
-// residuals to t.res, all shift-interleaved (a step's stores are m adjacent doubles per
-// array), and the first m with res <= tol to t.hits[s]; from then on the lane eliminates
-// nothing, so its running row stays row m*_s - 1's. A lane past t.m counts as stopped and
-// touches no memory. When every lane has stopped, lane 0 writes M = max m*_s to
-// flags[kFlagHit] and the element blocks stop the pass as k_p1_axpy_tol's do. A shift that
-// never stops keeps the pass running to k.
+// k_p1_axpy_tol with m lanes in the elimination workgroup's first wave: lane s eliminates
+// T_k + sig[s] I and keeps shift s's history and stop (stol_elim_wave, tpl_kstop.h). Once
+// flags[kFlagHit] holds M = max m*_s the element blocks stop the pass as k_p1_axpy_tol's do.
 template <int NP>
 __global__ __launch_bounds__(kTPB) void k_p1_axpy_stol(P1AxpyArgs a, launch::ShiftTol t) {
   __shared__ double red[4];
@@ -74,44 +52,7 @@ __global__ __launch_bounds__(kTPB) void k_p1_axpy_stol(P1AxpyArgs a, launch::Shi
   asm volatile("" ::"s"(W), "s"(r_cur), "s"(r_next), "s"(j), "s"(k), "s"(elim_block));
   if ((int)blockIdx.x == elim_block) {
     if (threadIdx.x >= 64 || j < 3) return;  // stol: the first wave, one lane per shift
-    const int i = j - 3;
-    const int s = threadIdx.x, m = t.m;
-    const bool lane = s < m;
-    const size_t am = (size_t)t.kcap * (size_t)m;  // one array of t.lu
-    const int stop = S.flags[0], done = S.flags[5];
-    const int every_hit = S.flags[kFlagHit];  // stol: M, written by an earlier launch
-    if (stop || done != i) return;  // breakdown at this step: k_ftk_inv_shifts finishes the rows
-    if (every_hit) return;          // stol: every running row stays where its lane stopped
-    int hit = lane ? t.hits[s] : 1;
-    if (lane && !hit) {
-      const double tol = t.tol[0], sg = t.sig[s];
-      const double dli = a.betas[i], d1 = S.alphas[i + 1] + sg, du1 = a.betas[i + 1];
-      LuRow cur{t.st[s], t.st[m + s], t.st[2 * m + s]};
-      double* D = t.lu + s;
-      if (i == 0) {
-        cur = LuRow{S.alphas[0] + sg, dli, 1.0};
-        const double r0 = fabs(dli * (cur.b / cur.d));  // the one-step iterate
-        t.res[s] = r0;
-        if (r0 <= tol) hit = 1;
-      }
-      lu_row(i * m, true, dli, d1, du1, cur, D, D + am, D + 2 * am, D + 3 * am);
-      t.st[s] = cur.d;
-      t.st[m + s] = cur.du;
-      t.st[2 * m + s] = cur.b;
-      // the (i + 2)-step iterate. A zero pivot gives inf or NaN, never <= a finite tol
-      const double r1 = fabs(du1 * (cur.b / cur.d));
-      t.res[(size_t)(i + 1) * m + s] = r1;
-      if (!hit && r1 <= tol) hit = i + 2;
-      if (hit) t.hits[s] = hit;
-      t.nres[s] = i + 2;
-    }
-    bool every;
-    const int mx = wave_hits(hit, every);
-    if (s == 0) {
-      S.flags[5] = i + 1;
-      S.flags[kFlagRes] = i + 2;
-      if (every) S.flags[kFlagHit] = mx;
-    }
+    stol_elim_wave(t, threadIdx.x, j, S.flags, S.alphas, a.betas);
     return;
   }
   const int rb = elem_block(A.G2, blockIdx.x);
@@ -181,51 +122,10 @@ __global__ __launch_bounds__(kTPB) void k_p1_axpy_stol(P1AxpyArgs a, launch::Shi
   if (threadIdx.x == 0) S.Pb[rb] = p;
 }
 
-// After the last step launch, one wave (k_p1_tol_fin's two cases, per lane). A pass of two
-// steps (kmax = 2, or a breakdown at step 3) never ran the elimination workgroup: lane s
-// forms its one residual by the same expression. And when the last launch's stops made every
-// lane stop (or this kernel's own just did), steps_taken becomes M here.
+// After the last step launch, one wave: stol_fin_wave (tpl_kstop.h) unless b was zero.
 __global__ void k_p1_stol_fin(DevState S, launch::ShiftTol t) {
   if (blockIdx.x != 0 || threadIdx.x >= 64 || S.flags[1]) return;
-  const int s = threadIdx.x;
-  const bool lane = s < t.m;
-  int hit = lane ? t.hits[s] : 1;
-  if (S.flags[kFlagHit] == 0 && S.flags[2] == 2 && S.flags[kFlagRes] == 0) {
-    if (lane) {
-      const double r0 = fabs(S.betas[0] * (1.0 / (S.alphas[0] + t.sig[s])));
-      t.res[s] = r0;
-      t.nres[s] = 1;
-      if (r0 <= t.tol[0]) {
-        hit = 1;
-        t.hits[s] = 1;
-      }
-    }
-    if (s == 0) S.flags[kFlagRes] = 1;
-  }
-  bool every;
-  const int mx = wave_hits(hit, every);
-  if (s == 0 && every) {
-    S.flags[kFlagHit] = mx;
-    S.flags[0] = 1;
-    S.flags[2] = mx;
-  }
-}
-
-// k_ftk_inv's division (tpl_kernels.hip: its comment holds): a / b given y = RN(1 / b) by
-// Markstein's correction where no intermediate leaves the normal range, else IEEE.
-__device__ __forceinline__ bool exp_in_range(double v) {
-  const unsigned e = (unsigned)(__double2hiint(v) >> 20) & 0x7FFu;  // biased exponent
-  return e - (1023u - 900u) <= 1800u;  // 2^-900 <= |v| < 2^901
-}
-__device__ __forceinline__ double div_rn(double a, double b, double y, bool b_ok) {
-  if (b_ok && exp_in_range(a)) {
-    const double q0 = a * y;
-    const double q = fma(fma(-b, q0, a), y, q0);
-    if (exp_in_range(q)) return q;
-  } else if (b_ok && a == 0.0) {
-    return a * y;  // +-0 with the quotient's sign
-  }
-  return a / b;
+  stol_fin_wave(t, threadIdx.x, S.flags, S.alphas, S.betas);
 }
 
 // Workgroup s: y_s = (T_n + sig[s] I)^{-1} e_1 with n = m*_s — t.hits[s], or steps_taken for
@@ -415,21 +315,9 @@ namespace launch {
 hipError_t p1_axpy_stol(const CsrDev& A, const DevState& S, const double* W, const double* r_cur,
                         double* r_next, int j, int k, const ShiftTol& t, hipStream_t s) {
   if (t.m < 1 || t.m > 64 || t.kcap < k) return hipErrorInvalidValue;
-  P1AxpyArgs a{};
-  a.Pa_r = S.Pa_r; a.W = W; a.r_cur = r_cur; a.r_next = r_next; a.flags = S.flags;
-  a.norms = S.norms; a.alphas = S.alphas; a.Pb = S.Pb; a.stamp = nullptr;
-  a.n = A.n; a.E = A.E; a.norm_n = A.norm_n; a.NA_r = A.NA_r; a.G2 = A.G2; a.j = j; a.k = k;
-  a.elim_block = g2_grid(A);  // the block after the element grid, padding blocks included
-  a.kcap = S.kcap; a.betas = S.betas; a.lu = S.lu;
+  const P1AxpyArgs a = p1_axpy_args(A, S, W, r_cur, r_next, j, k, g2_grid(A), nullptr);
   const dim3 g(g2_grid(A) + 1), b(kTPB);
-  if (A.NA_r <= 2 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy_stol<2>, g, b, 0, s, a, t);
-  else if (A.NA_r <= 4 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy_stol<4>, g, b, 0, s, a, t);
-  else if (A.NA_r <= 8 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy_stol<8>, g, b, 0, s, a, t);
-  else
-    hipLaunchKernelGGL(k_p1_axpy_stol<12>, g, b, 0, s, a, t);
+  TPL_NP_SWITCH(A.NA_r, hipLaunchKernelGGL(k_p1_axpy_stol<NP>, g, b, 0, s, a, t));
   return hipGetLastError();
 }
 hipError_t p1_stol_fin(const DevState& S, const ShiftTol& t, hipStream_t s) {

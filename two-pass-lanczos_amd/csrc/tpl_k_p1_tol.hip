@@ -13,28 +13,21 @@
 // The tolerance is read from device memory (tr[0]), not passed as an argument: the graph
 // is cached per kmax and replayed for any tolerance.
 //
-// k_p1_axpy_tol repeats k_p1_axpy's text (tpl_kernels.hip) with the additions marked
-// "tol:". The two are not one template: with the body factored out behind a compile-time
-// switch, the existing k_p1_axpy instances no longer compiled to the same instructions
-// (commuted operands, other registers in 227 of ~850 lines), and those are the headline's.
-// A change to k_p1_axpy's element part belongs here too.
+// Shared (tpl_kstop.h): the flag words of the stop and hit_before, the rule by which every
+// element block of a launch decides alike; lu_row (tpl_klu.h).
+// Still repeated: k_p1_axpy_tol repeats k_p1_axpy's text (tpl_kernels.hip) with the additions
+// marked "tol:". The two are not one template: with the body factored out behind a
+// compile-time switch, the existing k_p1_axpy instances no longer compiled to the same
+// instructions (commuted operands, other registers in 227 of ~850 lines), and those are the
+// headline's. Nor is its element part one inlined function with k_p1_axpy_stol's
+// (tpl_k_p1_stol.hip), though the two texts are the same: tried, 148 of this unit's 4,388
+// lines of assembly changed (commuted operands, moved instructions) in the element blocks,
+// the part every step waits for. A change to k_p1_axpy's element part belongs here too.
 #include "tpl_klaunch.h"
 #include "tpl_klu.h"
+#include "tpl_kstop.h"
 
 namespace tpl {
-
-// The tolerance stop's words of DevState::flags (k_p1_init leaves them alone; the host
-// zeroes them before the graph): [kFlagHit] the smallest m whose residual met the
-// tolerance, 0 if none yet; [kFlagRes] the entries of the residual history formed so far.
-constexpr int kFlagHit = 6;
-constexpr int kFlagRes = 7;
-// An element block of launch j acts on a hit only when an earlier launch wrote it: the hit
-// at m is written by launch m + 1 (m = 1 and 2: by launch 3, the first that eliminates).
-// Launch j's own elimination workgroup may be writing the word while the element blocks
-// read it; whichever value they see, this test gives every block the same answer.
-__device__ __forceinline__ bool hit_before(int hit, int j) {
-  return hit != 0 && j > (hit + 1 > 3 ? hit + 1 : 3);
-}
 
 // k_p1_axpy (tpl_kernels.hip: its comments hold for the shared text) with the tolerance
 // stop. tr = {tol, res[kcap]}. The elimination thread also forms the residual of the
@@ -67,7 +60,7 @@ __global__ __launch_bounds__(kTPB) void k_p1_axpy_tol(P1AxpyArgs a, double* tr) 
     double* D = a.lu;
     double* st = a.lu + 4 * kcap;
     double* res = tr + 1;
-    const int stop = S.flags[0], done = S.flags[5];
+    const int stop = S.flags[0], done = S.flags[kFlagDone];
     int hit = S.flags[kFlagHit];  // tol: written by an earlier launch of this workgroup
     const double tol = tr[0];
     const double dli = a.betas[i], d1 = S.alphas[i + 1], du1 = a.betas[i + 1];
@@ -85,7 +78,7 @@ __global__ __launch_bounds__(kTPB) void k_p1_axpy_tol(P1AxpyArgs a, double* tr) 
     st[0] = cur.d;
     st[1] = cur.du;
     st[2] = cur.b;
-    S.flags[5] = i + 1;
+    S.flags[kFlagDone] = i + 1;
     // tol: the (i + 2)-step iterate. A zero pivot gives inf or NaN, never <= a finite tol
     const double r1 = fabs(du1 * (cur.b / cur.d));
     res[i + 1] = r1;
@@ -187,21 +180,9 @@ namespace launch {
 
 hipError_t p1_axpy_tol(const CsrDev& A, const DevState& S, const double* W, const double* r_cur,
                        double* r_next, int j, int k, double* tr, hipStream_t s) {
-  P1AxpyArgs a{};
-  a.Pa_r = S.Pa_r; a.W = W; a.r_cur = r_cur; a.r_next = r_next; a.flags = S.flags;
-  a.norms = S.norms; a.alphas = S.alphas; a.Pb = S.Pb; a.stamp = nullptr;
-  a.n = A.n; a.E = A.E; a.norm_n = A.norm_n; a.NA_r = A.NA_r; a.G2 = A.G2; a.j = j; a.k = k;
-  a.elim_block = g2_grid(A);  // the block after the element grid, padding blocks included
-  a.kcap = S.kcap; a.betas = S.betas; a.lu = S.lu;
+  const P1AxpyArgs a = p1_axpy_args(A, S, W, r_cur, r_next, j, k, g2_grid(A), nullptr);
   const dim3 g(g2_grid(A) + 1), b(kTPB);
-  if (A.NA_r <= 2 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy_tol<2>, g, b, 0, s, a, tr);
-  else if (A.NA_r <= 4 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy_tol<4>, g, b, 0, s, a, tr);
-  else if (A.NA_r <= 8 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy_tol<8>, g, b, 0, s, a, tr);
-  else
-    hipLaunchKernelGGL(k_p1_axpy_tol<12>, g, b, 0, s, a, tr);
+  TPL_NP_SWITCH(A.NA_r, hipLaunchKernelGGL(k_p1_axpy_tol<NP>, g, b, 0, s, a, tr));
   return hipGetLastError();
 }
 hipError_t p1_tol_fin(const DevState& S, double* tr, hipStream_t s) {

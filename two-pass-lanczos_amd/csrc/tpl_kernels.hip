@@ -3,12 +3,22 @@
 //
 // Map of the device sources (one compile unit per .hip; tpl_launch.h declares every
 // launcher, the unit holding a kernel defines its launcher):
-//   tpl_kernels.hip     k_p1_init, k_p1_spmv, k_p1_axpy, k_ftk_inv (+ div_rn),
+//   tpl_kernels.hip     k_p1_init, k_p1_spmv, k_p1_axpy, k_ftk_inv,
 //                       k_p2_init, k_p2_coefs, k_p2_spmv, k_p2_tail, k_gemv_recon.
 //                       k_ftk_inv stays beside k_p1_axpy: both inline lu_row, and apart
 //                       k_p1_axpy's elimination branch compiles to other registers
 //   tpl_k_p1_tol.hip    k_p1_axpy_tol, k_p1_tol_fin (pass one of the inverse solve that stops
-//                       at a residual tolerance; lu_row itself: tpl_klu.h)
+//                       at a residual tolerance)
+//   tpl_k_p1_stol.hip   k_p1_axpy_stol, k_p1_stol_fin, k_ftk_inv_shifts, k_p2_xacc_cut (the
+//                       same for m shifts, each stopped on its own)
+//   tpl_k_batch_stol.hip  k_bp1_axpy_stol, k_bp1_stol_fin, k_bp2_xacc_cut (and for the columns
+//                       of a batch group)
+//   tpl_klu.h, tpl_kstop.h  what those four units share, each written once: lu_row; div_rn;
+//                       the stop's flag words, rule and vote; the shifted solves' elimination
+//                       lane and fin wave. Still repeated, because one inlined function moves
+//                       instructions of the instances that exist (the units' headers give the
+//                       figures): the element parts of k_p1_axpy, _tol and _stol and of
+//                       k_bp1_axpy and _stol, and the solve of k_ftk_inv and k_ftk_inv_shifts
 //   tpl_k_p2_cached.hip k_p2_cached (the two-pass solver's pass-two step whose long rows read
 //                       the sums its pass one kept: the long-row cache)
 //   tpl_k_spmv.hip      k_spmv (the plain product), k_permute
@@ -64,6 +74,7 @@
 #define TPL_LAB_TABLE 1  // this unit holds the stamp build's table (tpl_lab.h)
 #include "tpl_klaunch.h"
 #include "tpl_klu.h"
+#include "tpl_kstop.h"
 
 namespace tpl {
 
@@ -112,28 +123,8 @@ __global__ __launch_bounds__(kTPB, p1_min_waves(F, 1)) void k_p1_spmv(P1SpmvArgs
 // ---- T_k^{-1} e_1 on the device (the one-graph inv): the host solver's operations
 // (tpl_ftk.cpp: the LAPACK dgtsv scheme, tridiagonal elimination with partial pivoting,
 // then back substitution), bit for bit.
-// (LuRow, lu_row: tpl_klu.h, shared with k_p1_axpy_tol.)
-// a / b given y = RN(1 / b): Markstein's correction q = RN(q0 + RN(a - b q0) y), q0 =
-// RN(a y), is the correctly rounded quotient — the IEEE division's bits — whenever no
-// intermediate leaves the normal range; elsewhere (zeros, huge or tiny magnitudes,
-// non-finite values) the IEEE division itself. Three dependent operations instead of the
-// division's ten on the back substitution's chain. (Checked against IEEE division on
-// 10^9 random pairs in range, exact and binade-boundary quotients included: no
-// difference; tests/native/div_rn_check.c restates it on the host, tests/test_native.py)
-__device__ __forceinline__ bool exp_in_range(double v) {
-  const unsigned e = (unsigned)(__double2hiint(v) >> 20) & 0x7FFu;  // biased exponent
-  return e - (1023u - 900u) <= 1800u;  // 2^-900 <= |v| < 2^901
-}
-__device__ __forceinline__ double div_rn(double a, double b, double y, bool b_ok) {
-  if (b_ok && exp_in_range(a)) {
-    const double q0 = a * y;
-    const double q = fma(fma(-b, q0, a), y, q0);
-    if (exp_in_range(q)) return q;
-  } else if (b_ok && a == 0.0) {
-    return a * y;  // +-0 with the quotient's sign
-  }
-  return a / b;
-}
+// (LuRow, lu_row: tpl_klu.h, shared with the elimination lanes of the tolerance stops.)
+// (div_rn, the back substitution's division: tpl_kstop.h, shared with k_ftk_inv_shifts.)
 
 // Pass one / standard, step j: alpha_j; r_{j+1} = w - alpha_j v_j; ||r_{j+1}||^2 partials.
 // NP: alpha partials loaded per thread up front (the launcher picks the smallest of 2, 4,
@@ -145,8 +136,8 @@ __device__ __forceinline__ double div_rn(double a, double b, double y, bool b_ok
 // so only the last rows and the back substitution remain after pass one (k_ftk_inv).
 // That workgroup is block a.elim_block, the one after the element grid (its padding
 // blocks included, so never one elem_block maps to a row block or to -1); -1: none.
-// k_p1_axpy_tol (tpl_k_p1_tol.hip) repeats this kernel's text with the tolerance stop added:
-// a change to the body below belongs there too.
+// k_p1_axpy_tol (tpl_k_p1_tol.hip) and k_p1_axpy_stol (tpl_k_p1_stol.hip) repeat this
+// kernel's text with the tolerance stop added: a change to the body below belongs there too.
 template <int NP>
 __global__ __launch_bounds__(kTPB) void k_p1_axpy(P1AxpyArgs a) {
   __shared__ double red[4];
@@ -547,22 +538,10 @@ hipError_t p1_spmv(const CsrDev& A, const DevState& S, const double* xsrc, const
 hipError_t p1_axpy(const CsrDev& A, const DevState& S, const double* W, const double* r_cur,
                    double* r_next, int j, int k, int elim, hipStream_t s,
                    unsigned long long* st) {
-  P1AxpyArgs a{};
-  a.Pa_r = S.Pa_r; a.W = W; a.r_cur = r_cur; a.r_next = r_next; a.flags = S.flags;
-  a.norms = S.norms; a.alphas = S.alphas; a.Pb = S.Pb; a.stamp = st;
-  a.n = A.n; a.E = A.E; a.norm_n = A.norm_n; a.NA_r = A.NA_r; a.G2 = A.G2; a.j = j; a.k = k;
   // the elimination workgroup: the block after the element grid, padding blocks included
-  a.elim_block = elim ? g2_grid(A) : -1;
-  a.kcap = S.kcap; a.betas = S.betas; a.lu = S.lu;
+  const P1AxpyArgs a = p1_axpy_args(A, S, W, r_cur, r_next, j, k, elim ? g2_grid(A) : -1, st);
   const dim3 g(g2_grid(A) + (elim ? 1 : 0)), b(kTPB);
-  if (A.NA_r <= 2 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy<2>, g, b, 0, s, a);
-  else if (A.NA_r <= 4 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy<4>, g, b, 0, s, a);
-  else if (A.NA_r <= 8 * kTPB)
-    hipLaunchKernelGGL(k_p1_axpy<8>, g, b, 0, s, a);
-  else
-    hipLaunchKernelGGL(k_p1_axpy<12>, g, b, 0, s, a);
+  TPL_NP_SWITCH(A.NA_r, hipLaunchKernelGGL(k_p1_axpy<NP>, g, b, 0, s, a));
   return hipGetLastError();
 }
 hipError_t p2_init(int64_t n, const DevState& S, const double* b, double* v1, double* x,

@@ -30,6 +30,27 @@ static inline size_t spmv_lds_bytes(const CsrDev& A) {
   const size_t win = (size_t)A.s_win * sizeof(double);  // short-chunk column window
   return bins > win ? bins : win;
 }
+// The arguments of a pass-one AXPY step (k_p1_axpy, k_p1_axpy_tol, k_p1_axpy_stol).
+// elim_block: the elimination workgroup's block — g2_grid(A), the block after the element
+// grid, padding blocks included — or -1 for none.
+static inline P1AxpyArgs p1_axpy_args(const CsrDev& A, const DevState& S, const double* W,
+                                      const double* r_cur, double* r_next, int j, int k,
+                                      int elim_block, unsigned long long* stamp) {
+  P1AxpyArgs a{};
+  a.Pa_r = S.Pa_r; a.W = W; a.r_cur = r_cur; a.r_next = r_next; a.flags = S.flags;
+  a.norms = S.norms; a.alphas = S.alphas; a.Pb = S.Pb; a.stamp = stamp;
+  a.n = A.n; a.E = A.E; a.norm_n = A.norm_n; a.NA_r = A.NA_r; a.G2 = A.G2; a.j = j; a.k = k;
+  a.elim_block = elim_block;
+  a.kcap = S.kcap; a.betas = S.betas; a.lu = S.lu;
+  return a;
+}
+// CALL with NP a constant expression: the smallest of 2, 4, 8, 12 with kTPB NP >= na_r (12
+// for more: the step reduces the rest in batches), the alpha partials a thread loads up front.
+#define TPL_NP_SWITCH(na_r, CALL)                                   \
+  if ((na_r) <= 2 * kTPB) { constexpr int NP = 2; CALL; }           \
+  else if ((na_r) <= 4 * kTPB) { constexpr int NP = 4; CALL; }      \
+  else if ((na_r) <= 8 * kTPB) { constexpr int NP = 8; CALL; }      \
+  else { constexpr int NP = 12; CALL; }
 // launch_f(std::integral_constant<int, F>) for the F equal to f, over the instances that
 // exist; hipErrorInvalidConfiguration when f has none, else the launch's status.
 template <class LaunchF, int... Fs>

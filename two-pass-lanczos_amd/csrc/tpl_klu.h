@@ -1,6 +1,7 @@
 // tpl_klu.h — one row of the tridiagonal elimination of T_k's LU (the dgtsv scheme of
 // tpl_ftk.cpp), shared by every kernel that runs it: k_p1_axpy's elimination workgroup and
-// k_ftk_inv (tpl_kernels.hip), k_p1_axpy_tol (tpl_k_p1_tol.hip).
+// k_ftk_inv (tpl_kernels.hip), k_p1_axpy_tol (tpl_k_p1_tol.hip), the shifted solves' lanes
+// (stol_elim_wave, tpl_kstop.h) and k_ftk_inv_shifts (tpl_k_p1_stol.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -71,7 +71,7 @@ hipError_t p2_xacc_cut(const CsrDev& A, const double* Y, int ldy, int j, int nfl
 struct BatchShiftTol {
   ShiftTol t0;
   size_t dstride, istride;
-  ShiftTol col(int c) const {
+  __host__ __device__ ShiftTol col(int c) const {  // the kernels' wave c calls it too
     ShiftTol v = t0;
     v.st += (size_t)c * dstride;
     v.lu += (size_t)c * dstride;

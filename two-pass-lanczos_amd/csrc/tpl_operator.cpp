@@ -443,17 +443,28 @@ void ensure_exp_times(tpl_op_s* op) {
     HIPCHK(hipHostMalloc((void**)&op->h_exp_back, TPL_MULTI_MAX * sizeof(int32_t),
                          hipHostMallocDefault));
 }
+namespace {
+// A tolerance-stop family's device block and its pinned mirror, replaced by a zeroed block of
+// dev_bytes and a mirror of host_bytes. The graphs hold the old block's pointer and go with it
+// (a first allocation drops nothing). The caller zeroes its capacities before and sets them
+// after: a refused allocation leaves them zero, so the next call starts over.
+void replace_stop_block(tpl_op_s* op, double*& dev, void*& host, size_t dev_bytes,
+                        size_t host_bytes) {
+  if (dev) drop_graphs(op);
+  dev_free(op, dev);
+  if (host) hipHostFree(host);
+  host = nullptr;
+  dev_alloc(op, &dev, dev_bytes);
+  dev_zero(op, dev, dev_bytes);
+  HIPCHK(hipHostMalloc(&host, host_bytes, hipHostMallocDefault));
+}
+} // namespace
 void ensure_tol(tpl_op_s* op) {
   const size_t kc = op->st.kcap;
   if (op->d_tol && op->tol_cap == kc) return;
-  if (op->d_tol) drop_graphs(op);  // they hold the pointer being replaced
-  dev_free(op, op->d_tol);
-  if (op->h_tol) hipHostFree(op->h_tol);
-  op->h_tol = nullptr;
   op->tol_cap = 0;
-  dev_alloc(op, &op->d_tol, (1 + kc) * sizeof(double));
-  dev_zero(op, op->d_tol, (1 + kc) * sizeof(double));
-  HIPCHK(hipHostMalloc(&op->h_tol, kFlagBytes + kc * sizeof(double), hipHostMallocDefault));
+  replace_stop_block(op, op->d_tol, op->h_tol, (1 + kc) * sizeof(double),
+                     kFlagBytes + kc * sizeof(double));
   op->tol_cap = kc;
 }
 void ensure_col_steps(tpl_op_s* op) {
@@ -465,18 +476,11 @@ launch::ShiftTol ensure_stol(tpl_op_s* op, size_t m) {
   const size_t kc = op->st.kcap;
   if (!op->d_stol || op->stol_cap != kc || op->stol_m < m) {
     const size_t mc = std::max(m, op->stol_m);
-    if (op->d_stol) drop_graphs(op);  // they hold the pointers being replaced
-    dev_free(op, op->d_stol);
-    if (op->h_stol) hipHostFree(op->h_stol);
-    op->h_stol = nullptr;
     op->stol_m = op->stol_cap = 0;
     const size_t doubles = 1 + mc * (4 + 5 * kc);
-    const size_t bytes = doubles * sizeof(double) + 2 * mc * sizeof(int32_t);
-    dev_alloc(op, &op->d_stol, bytes);
-    dev_zero(op, op->d_stol, bytes);
-    HIPCHK(hipHostMalloc(&op->h_stol,
-                         kFlagBytes + 2 * mc * sizeof(int32_t) + kc * mc * sizeof(double),
-                         hipHostMallocDefault));
+    replace_stop_block(op, op->d_stol, op->h_stol,
+                       doubles * sizeof(double) + 2 * mc * sizeof(int32_t),
+                       kFlagBytes + 2 * mc * sizeof(int32_t) + kc * mc * sizeof(double));
     op->stol_m = mc;
     op->stol_cap = kc;
   }
@@ -576,18 +580,11 @@ launch::BatchShiftTol ensure_batch_stol(tpl_op_s* op, size_t m) {
   const size_t kc = b.kcap, w = (size_t)kBatchNbMax;
   if (!b.d_stol || b.stol_m < m) {
     const size_t mc = std::max(m, b.stol_m);
-    if (b.d_stol) drop_graphs(op);  // they hold the pointers being replaced
-    dev_free(op, b.d_stol);
-    if (b.h_stol) hipHostFree(b.h_stol);
-    b.h_stol = nullptr;
     b.stol_m = 0;
     const size_t doubles = 1 + mc + w * mc * (3 + 5 * kc);
-    const size_t bytes = doubles * sizeof(double) + w * 2 * mc * sizeof(int32_t);
-    dev_alloc(op, &b.d_stol, bytes);
-    dev_zero(op, b.d_stol, bytes);
-    HIPCHK(hipHostMalloc(&b.h_stol,
-                         w * (kFlagBytes + 2 * mc * sizeof(int32_t) + kc * mc * sizeof(double)),
-                         hipHostMallocDefault));
+    replace_stop_block(op, b.d_stol, b.h_stol,
+                       doubles * sizeof(double) + w * 2 * mc * sizeof(int32_t),
+                       w * (kFlagBytes + 2 * mc * sizeof(int32_t) + kc * mc * sizeof(double)));
     b.stol_m = mc;
   }
   // the arrays are laid out for the capacity; their inner stride is this call's m
