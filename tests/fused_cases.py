@@ -28,9 +28,9 @@ def hub_arcs(hubs, span=8):
     return t, h
 
 
-def kkt_hubs(hubs=30, leaves=0, d=False):
+def kkt_hubs(hubs=30, leaves=0, d=False, span=8):
     """`hubs` hub nodes and `leaves` nodes of degree 1, each hanging on a hub by one arc."""
-    t, h = hub_arcs(hubs)
+    t, h = hub_arcs(hubs, span)
     t = np.concatenate([t, hubs + np.arange(leaves)])
     h = np.concatenate([h, np.arange(leaves) % hubs])
     return kkt_from_arcs(hubs + leaves, t, h, 2.0 + np.arange(len(t)) % 3 if d else None)

@@ -30,6 +30,7 @@ FLAG_MASK = ONE_GRAPH | CACHED | FUSED
 
 MATRICES = ("kkt", "band")
 N_COLS = 7
+DENSE_EIG_MAX = 4096             # Inputs.eigenvectors5: rows up to which it decomposes densely
 
 # tpl.h entry points the catalogue leaves out on purpose (tests/test_call_order_cpu.py)
 NOT_COVERED = {
@@ -72,21 +73,18 @@ class Inputs:
     stop early, and the batch ones a column that runs to kmax beside one that has stopped
     (tests/test_call_order_cpu.py asserts this mix on the host)."""
 
-    def __init__(self, name):
-        from oracle.rng import std_rng_vector
+    def __init__(self, name, a=None, schedule=None, B=None):
+        """a: the matrix (default: matrix(name)). schedule: the reduction order the host
+        decompositions are made in (default: a default operator's, from a host plan).
+        B: right_hand_sides(a) made earlier (tests/geometry_cases.py: one matrix under
+        several schedules)."""
         self.name = name
-        self.a = a = matrix(name)
+        self.a = a = matrix(name) if a is None else a
         n = self.n = a.shape[0]
-        r0 = std_rng_vector(n) - 0.5
-        rng = np.random.default_rng(3)
-        r1, r2 = rng.standard_normal(n), rng.standard_normal(n)
-        _, v = np.linalg.eigh(a.toarray())
-        idx = [n // 10, 3 * n // 10, n // 2, 7 * n // 10, 9 * n // 10]
-        inv5 = v[:, idx] @ np.array([1.0, -0.7, 0.5, 1.3, -0.9])
-        self.B = np.asfortranarray(np.stack([r0, inv5, a @ (a @ r0), r1, a @ r1, np.ones(n),
-                                             1e-3 * r2], axis=1))
+        self.B = self.right_hand_sides(a) if B is None else B
+        assert self.B.shape == (n, N_COLS)
         self.b = np.ascontiguousarray(self.B[:, 0])
-        self._dec, self._orc = {}, None
+        self._dec, self._orc, self._schedule = {}, None, schedule
         self._dev = {}
         # 0.0 (two_pass_inv_tol_never) is never met: a residual is <= 0 only when it is 0
         from tpl_amd import ftk
@@ -95,17 +93,53 @@ class Inputs:
         self.tol_mix = 0.5 * float(np.min(self.history(0, K_BIG, SIGMA_MIN)))
         assert self.tol_met > 0.0 and self.tol_mix > 0.0
 
+    @staticmethod
+    def eigenvectors5(a):
+        """Five eigenvectors of a spread over its spectrum. Up to DENSE_EIG_MAX rows those at
+        the positions n/10, 3n/10, n/2, 7n/10 and 9n/10 of the dense decomposition; above it
+        (a dense one takes half a minute at 10,000 rows) the eigenvector nearest each of those
+        quantiles of the diagonal, by shift-and-invert Lanczos from the constant vector."""
+        n = a.shape[0]
+        if n <= DENSE_EIG_MAX:
+            _, v = np.linalg.eigh(a.toarray())
+            return v[:, [n // 10, 3 * n // 10, n // 2, 7 * n // 10, 9 * n // 10]]
+        from scipy.sparse.linalg import eigsh
+        diag = np.sort(a.diagonal())
+        found = [eigsh(a.tocsc(), k=1, sigma=float(diag[i]), v0=np.ones(n))
+                 for i in (n // 10, 3 * n // 10, n // 2, 7 * n // 10, 9 * n // 10)]
+        lam = np.array([w[0] for w, _ in found])
+        assert np.all(np.diff(lam) > 1e-8 * np.abs(lam).max()), lam   # five different ones
+        return np.stack([v[:, 0] for _, v in found], axis=1)
+
+    @staticmethod
+    def right_hand_sides(a):
+        from oracle.rng import std_rng_vector
+        n = a.shape[0]
+        r0 = std_rng_vector(n) - 0.5
+        rng = np.random.default_rng(3)
+        r1, r2 = rng.standard_normal(n), rng.standard_normal(n)
+        inv5 = Inputs.eigenvectors5(a) @ np.array([1.0, -0.7, 0.5, 1.3, -0.9])
+        return np.asfortranarray(np.stack([r0, inv5, a @ (a @ r0), r1, a @ r1, np.ones(n),
+                                           1e-3 * r2], axis=1))
+
     def oracle(self):
         if self._orc is None:
             import oracle
-            import tpl_amd
-            plan = tpl_amd.operator.HostPlan(self.a)
-            self._orc = oracle.Operator(self.a, plan.schedule())
-            plan.close()
+            if self._schedule is None:
+                import tpl_amd
+                plan = tpl_amd.operator.HostPlan(self.a)
+                self._schedule = plan.schedule()
+                plan.close()
+            self._orc = oracle.Operator(self.a, self._schedule)
         return self._orc
 
+    def oracle_schedule(self):
+        self.oracle()
+        return self._schedule
+
     def dec(self, c, k):
-        """Column c's k-step decomposition (host, device order of a default operator)."""
+        """Column c's k-step decomposition (host, in the oracle's reduction order: a default
+        operator's unless a schedule was handed in)."""
         if (c, k) not in self._dec:
             from tpl_amd import algorithms as alg
             al, be, st, bn, _ = self.oracle().pass_one(self.B[:, c], k)
@@ -245,6 +279,16 @@ def same(x, y):
         elif p.shape != q.shape or not np.array_equal(p, q):
             return False
     return True
+
+
+def same_schedule(x, y):
+    """Two schedule dicts (HipCsrOp.schedule(), conftest.canon_schedule) name one layout."""
+    def eq(p, q):
+        return (p is None) == (q is None) and (p is None or np.array_equal(p, q))
+    return (int(x["G2"]), int(x["E"]), int(x["slices"])) == (int(y["G2"]), int(y["E"]),
+                                                             int(y["slices"])) and \
+        eq(x["short_rows"], y["short_rows"]) and eq(x["long_rows"], y["long_rows"]) and \
+        eq(x["perm"], y["perm"])
 
 
 def _dec_tuple(d):
@@ -516,9 +560,12 @@ SETTINGS = {
     "reorder": ("tpl_op_set_reorder", 2, (0, 1)),
     "order_groups": ("tpl_op_set_order_groups", 0, (4,)),
     "timing": ("tpl_op_enable_timing", 0, (1,)),
+    # one row block: the band's element grid goes from G2 3, E 512 to G2 1, E 1536 and back (the
+    # KKT block's 496 rows are one block of 512 either way)
+    "max_g2": ("tpl_op_set_schedule", 1024, (1,)),
 }
 SETTING_NAMES = tuple(SETTINGS)
-LAYOUT_SETTERS = ("value_format", "slices", "short_row_max", "reorder", "order_groups")
+LAYOUT_SETTERS = ("value_format", "slices", "short_row_max", "reorder", "order_groups", "max_g2")
 DEFAULT_SETTINGS = tuple(SETTINGS[n][1] for n in SETTING_NAMES)
 
 
@@ -549,6 +596,8 @@ def apply_setting(op, name, value):
         op.set_order_groups(value)
     elif name == "timing":
         op.enable_timing(bool(value))
+    elif name == "max_g2":
+        op.set_schedule(max_g2=value)
     else:
         raise KeyError(name)
 
@@ -578,7 +627,9 @@ def anchor(mat, settings):
     bit, wherever the oracle has a counterpart — apply, pass one, the two-pass and one-pass
     inverse solves, both re-orthogonalised passes — so that `fresh` is not anchored in the
     code under test alone. On default settings also the path flags the matrices were chosen
-    for: the KKT block's two-pass solve runs fused, the band's reads the cache unfused."""
+    for (the KKT block's two-pass solve runs fused, the band's reads the cache unfused) and,
+    at the default sizes, every call tests/composed_oracle.py composes from the oracle — the
+    whole catalogue but the ftk_*device calls."""
     if (mat, settings) in _ANCHORED:
         return
     import oracle
@@ -609,8 +660,22 @@ def anchor(mat, settings):
         if settings == DEFAULT_SETTINGS:
             want = CACHED | FUSED if mat == "kkt" else CACHED
             assert flags & (CACHED | FUSED) == want, (mat, flags)
+            default_schedule = op.schedule()
     finally:
         op.close()
+    if settings == DEFAULT_SETTINGS:
+        # every call the oracle can compose (tests/composed_oracle.py), at the default sizes,
+        # each on an operator of its own: `fresh` rests on the oracle for the whole catalogue
+        import composed_oracle as co
+        assert same_schedule(default_schedule, I.oracle_schedule()), mat
+        for name in co.covered():
+            p = calls()[name].params()
+            op = new_op(mat, settings)
+            try:
+                want = co.canonical_expect(name, I, p, op)
+                assert same(run_call(op, mat, name, p)[0], want), (mat, name, p)
+            finally:
+                op.close()
     _ANCHORED.add((mat, settings))
 
 
@@ -652,7 +717,7 @@ def walk(seed):
     """The step list of one walk: ("call", name, params) or ("set", name, value). About a fifth
     of the steps are setters. Every walk opens with a small call that a later step outgrows in
     k and in m, and holds a layout rebuild followed at once by a batch call; walk `seed` also
-    holds the catalogue's calls seed, seed + 16, ... and setter seed mod 10, so the 16 walks
+    holds the catalogue's calls seed, seed + 16, ... and setter seed mod 11, so the 16 walks
     cover every call and every setter."""
     rng = random.Random(7919 * seed + 13)
     names = call_names()

@@ -19,10 +19,12 @@ Measured figures of the checks that carry a bound: none — every comparison is 
 
 Executed: 38 calls, so 2 x 38 x 38 = 2,888 ordered pairs (8,664 compared calls); 576 ladder steps
 and the same 576 again with a compared call of another family after each (1,728 compared calls);
-14 setter values x 7 calls x 2 matrices x 3 calls; 16 walks x 40 steps x 2 matrices = 1,280 steps,
-1,038 of them calls and 242 setters. No flag bit is masked beyond Call.defines.
+15 setter values x 7 calls x 2 matrices x 3 calls (max_g2 = 1 among them: the band's element grid
+goes from three row blocks of 512 to one of 1536 and back); 16 walks x 40 steps x 2 matrices =
+1,280 steps, 1,028 of them calls and 252 setters. No flag bit is masked beyond Call.defines.
+`fresh` itself is anchored in the oracle for all 33 calls tests/composed_oracle.py composes.
 
-Wall time on one MI355X: this file 14.8 s for its 117 cases (the slowest case 0.9 s, the first,
+Wall time on one MI355X: this file 15.2 s for its 118 cases (the slowest case 1.1 s, the first,
 which fills `fresh`); tests/test_call_order_cpu.py 2.2 s on the host; the whole `-m gpu` run of
 the commit before this file 190 s (1,554 cases), with it 208 s (1,671).
 
